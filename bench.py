@@ -27,6 +27,14 @@ one engine per visible GPU, merged by ksa_allreduce_state / ksa_scan_allstitch (
 Launch: under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or plainly as
 `python bench.py --gpus N`: the parent then starts N fresh rank processes itself (before it has touched the GPU),
 relays rank 0's JSON line and fails if any rank fails.  Rank 0 prints ONE JSON line on stdout.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (its `roofline` block comes from the
+same timed steps).  `--full` adds what takes runs of its own: the one-core and multi-core CPU baselines and, for the
+config-2 headline, the short runs of the other configurations (`secondary_configs`); `--no-cpu` / `--no-secondary`
+drop either from a `--full` run.  `--dump-outputs DIR` writes what the timed path computed in its last step as
+DIR/<name>.npy (float32): the Cur/Max/Min/Avg curves and the waterfall ring and, for the zeroSpan configs, a fixed
+seeded sample of the per-frame dB rows and waterfall rows (at most 64 MB in all).  The inputs depend only on the
+arguments, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -347,6 +355,38 @@ def state_digest(st):
     return h.hexdigest()
 
 
+# ------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_ROWS_BYTES = 24 << 20     # the widest sampled per-frame array; curves + ring + the sampled rows stay under 64 MB
+DUMP_SEED = 20201226
+
+
+def state_outputs(st):
+    """The plotting hand-off (Cur/Max/Min/Avg + waterfall ring) as float32 arrays: the library's own precision."""
+    out = {"fft_" + k[4:].lower(): np.asarray(st[k], dtype=np.float32) for k in ("Fft.Cur", "Fft.Max", "Fft.Min", "Fft.Avg")}
+    out["fft_hm"] = np.asarray(st["fftHM"], dtype=np.float32)
+    return out
+
+
+def sample_frames(frames, width):
+    """A fixed, seeded, sorted sample of frame indices whose rows of `width` floats fit the budget (all frames when they fit)."""
+    k = min(frames, max(1, DUMP_ROWS_BYTES // (4 * width)))
+    return np.arange(frames) if k == frames else np.sort(np.random.default_rng(DUMP_SEED).choice(frames, k, replace=False))
+
+
+def take_rows(torch, rows_dev, idx):
+    """Rows `idx` of a device array [frames, width] as float32 on the host."""
+    return rows_dev.index_select(0, torch.from_numpy(idx).to(rows_dev.device)).float().cpu().numpy()
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    sys.stderr.write("bench.py: wrote %d arrays (%.1f MB) to %s\n" % (len(arrays), total / 1e6, path))
+
+
 def ranks_block(torch, dist, backend, world, local):
     """Every rank reports itself; rank 0 receives the list.  `distinct_devices` counts (host, bus id / uuid / ordinal)."""
     mine = dict(device_identity(torch, local), rank=dist.get_rank(), local_rank=int(os.environ.get("LOCAL_RANK", "0")))
@@ -367,18 +407,25 @@ def parse_args():
     ap.add_argument("--frames", type=int, default=None, help="zeroSpan configs: capture blocks per GPU per step")
     ap.add_argument("--passes", type=int, default=None, help="scan configs: whole passes per step")
     ap.add_argument("--fmt", choices=("c64", "u8"), default="c64")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines and, for config 2, the short runs of configs 3, 4, 5 and of uint8 input")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="length of each of the 5 CPU measurements")
     ap.add_argument("--cpu-workers", type=int, default=16,
                     help="processes of the multi-core CPU figure (capped by the usable cores; 16 = the CPU share of a one-GPU box)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="headline run on one GPU: skip the short runs of the other BASELINE configurations (3, 4, 5)")
+                    help="--full headline run on one GPU: skip the short runs of the other BASELINE configurations (3, 4, 5)")
     ap.add_argument("--force-collective", action="store_true",
                     help="N=1, zeroSpan only: run the multi-GPU merge path on a one-rank group, to price its fixed cost")
     ap.add_argument("--inprocess", action="store_true",
                     help="ONE process, --gpus engines placed on the visible devices (engine r on device r %% device_count), merged by "
                          "ksa_allreduce_state / ksa_scan_allstitch: the torch-free multi-GPU form (no RCCL)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def roofline_block(cfg, args, eng, units_per_step, kern_ms, launches, step_s):
@@ -550,6 +597,13 @@ def main():
     kern_ms, launches = eng.prof_read()
     eng.prof_enable(False)
 
+    # ---- what the last timed step computed (zeroSpan: read before the strong sub-run below overwrites it)
+    dump = args.dump_outputs is not None and rank == 0
+    if dump and cfg["mode"] == "zerospan":
+        idx = sample_frames(frames, n)         # the same frames of both per-frame arrays (the ring is narrower: W <= N)
+        outputs = dict(state_outputs(eng.state()), cur_db=take_rows(torch, cur_db, idx), hm_rows=take_rows(torch, hm_rows, idx))
+        write_outputs(args.dump_outputs, outputs)
+
     # ---- after the timed region: does every rank hold the same result?  (scan: after assembling the sharded curves)
     proof = None
     if world > 1:
@@ -558,6 +612,8 @@ def main():
         dist.all_gather_object(digests, state_digest(st))
         proof = {"state_identical_across_ranks": len(set(digests)) == 1, "state_sha256_rank0": digests[0],
                  "ranks_differing_from_rank0": [r for r, dg in enumerate(digests) if dg != digests[0]]}
+    if dump and cfg["mode"] == "scan":
+        write_outputs(args.dump_outputs, state_outputs(st if world > 1 else eng.scan_state()))
     strong = None
     if strong_step is not None:
         fs, sfn = strong_step
@@ -597,12 +653,12 @@ def main():
                 "" if ranks["distinct_devices"] == world else " -- a functional REHEARSAL of the launch path on shared devices, not a scaling measurement"))
             if strong is not None:
                 out["strong"] = strong
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(cfg, nwin, args.cpu_seconds)
             multi = cpu_baseline_multicore(args.config, nwin, args.cpu_seconds, max_workers=args.cpu_workers)
             if multi is not None:
                 out["cpu_baseline_multicore"] = multi
-        if world == 1 and args.config == 2 and not args.no_secondary and not args.force_collective:
+        if world == 1 and args.full and args.config == 2 and not args.no_secondary and not args.force_collective:
             out["secondary_configs"] = secondary_configs(args.fmt)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
@@ -701,13 +757,16 @@ def main_inprocess(args):
     sync_all()
     dt = time.perf_counter() - t0
     if cfg["mode"] == "zerospan":
-        digests = [state_digest(eng.state()) for eng in engines]
+        states = [eng.state() for eng in engines]
     else:
         curves = ksa.scan_gather_state(engines, steps)
-        digests = []
+        states = []
         for eng in engines:
             st = eng.scan_state()
-            digests.append(state_digest(dict(curves, fftHM=st["fftHM"], hm_index=st["hm_index"])))
+            states.append(dict(curves, fftHM=st["fftHM"], hm_index=st["hm_index"]))
+    digests = [state_digest(st) for st in states]
+    if args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, state_outputs(states[0]))
     nwin = engines[0].num_windows
     idents = [dict(device_identity(torch, dv), engine=r) for r, dv in enumerate(devs)]
     distinct = len(set(devs))

@@ -151,13 +151,13 @@ def test_zero_span_from_raw_rtl_sdr_capture(tmp_path):
 
 def test_bench_contract_one_json_line():
     """bench.py prints exactly one line on stdout -- the JSON the driver parses -- with the contract's keys, the
-    roofline and cpu_baseline objects, and nothing else there (RCCL and friends are kept on stderr)."""
+    roofline and (--full) cpu_baseline objects, and nothing else there (RCCL and friends are kept on stderr)."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--frames", "2048", "--cpu-seconds", "1", "--force-collective"],
+                        "--frames", "2048", "--cpu-seconds", "1", "--force-collective", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
@@ -174,3 +174,40 @@ def test_bench_contract_one_json_line():
     assert abs(d["value"] - 2048 * 15 * 3 / (d["ms_per_step"] * 3 / 1e3)) / d["value"] < 1e-9
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["unit"] == "FFT/s" and cb["value"] > 0 and cb["sample"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run carries neither the CPU baselines nor the side runs (those need --full); --dump-outputs writes the
+    last timed step's curves, ring and sampled per-frame rows, and two runs with the same arguments write the same bits."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--frames", "512", "--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(r.stdout.splitlines()) == 1, r.stdout
+        lines.append(json.loads(r.stdout))
+    d = lines[0]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["roofline"]["launches"] == 2
+    assert abs(d["value"] - 512 * 15 * 2 / (d["ms_per_step"] * 2 / 1e3)) / d["value"] < 1e-9
+    for k in ("cpu_baseline", "cpu_baseline_multicore", "secondary_configs"):
+        assert k not in d, k
+    want = {"fft_cur": (4096,), "fft_max": (4096,), "fft_min": (4096,), "fft_avg": (4096,), "fft_hm": (128, 512),
+            "cur_db": (512, 4096), "hm_rows": (512, 512)}
+    names = sorted(p.name for p in (tmp_path / "0").iterdir())
+    assert names == sorted(k + ".npy" for k in want), names
+    total = 0
+    for name, shape in want.items():
+        a, b = np.load(tmp_path / "0" / (name + ".npy")), np.load(tmp_path / "1" / (name + ".npy"))
+        assert a.shape == shape and a.dtype == np.float32, (name, a.shape, a.dtype)
+        assert np.array_equal(a, b, equal_nan=True), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    # the last step's per-frame dB rows hold the spectrum of the synthetic tones: finite, and Max >= Cur >= Min
+    cur = np.load(tmp_path / "0" / "cur_db.npy")
+    assert np.isfinite(cur).all()
+    mx, mn, cu = (np.load(tmp_path / "0" / (k + ".npy")) for k in ("fft_max", "fft_min", "fft_cur"))
+    assert np.all(mx >= cu) and np.all(cu >= mn)

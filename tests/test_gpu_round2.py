@@ -372,7 +372,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu(cfg, extra, units):
 
 @pytest.mark.parametrize("cfg,extra", [(3, ["--passes", "8"]), (4, ["--passes", "16"]), (5, ["--frames", "16"])])
 def test_bench_secondary_configs_one_gpu(cfg, extra):
-    d = _bench(["--config", str(cfg), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.3"] + extra)
+    d = _bench(["--config", str(cfg), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.3", "--full"] + extra)
     assert d["config"]["baseline_config"] == cfg and d["n_gpus"] == 1 and d["unit"] == "FFT/s"
     rf = d["roofline"]
     assert rf["bound"] == {3: "valu", 4: "valu", 5: "hbm (Z round trip)"}[cfg] and rf["limiter"] and 0 < rf["frac"] < 1 and 0 < rf["flop_frac"] < 1 and rf["frac_step"] <= rf["frac"] * 1.001

@@ -352,9 +352,9 @@ def test_bench_self_launch_many_ranks_on_one_gpu(cfg, gpus, extra, units):
 
 
 def test_bench_headline_line_carries_the_secondary_configs():
-    """The default (driver) form of bench.py: the headline line of config 2 plus a short run of configs 3, 4, 5 each,
-    so that every BASELINE configuration has a driver-run number in the record."""
-    d = _bench(["--frames", "2048", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.3"], timeout=1200)
+    """The --full form of bench.py: the headline line of config 2 plus a short run of configs 3, 4, 5 each,
+    so that every BASELINE configuration has a number in the record."""
+    d = _bench(["--frames", "2048", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.3", "--full"], timeout=1200)
     assert d["config"]["baseline_config"] == 2 and d["n_gpus"] == 1
     sec = d["secondary_configs"]
     assert sorted(sec) == ["2:u8", "3", "4", "5"]

@@ -336,6 +336,33 @@ def test_limiter_quotes_its_own_fields():
     assert bench.backend_name("nccl").startswith("RCCL") and bench.backend_name("gloo").startswith("gloo")
 
 
+def test_bench_dump_helpers(tmp_path, monkeypatch):
+    """--dump-outputs: the hand-off curves and ring as float32 .npy files, and a fixed, seeded, sorted sample of the
+    per-frame rows once they exceed the budget (all rows while they fit)."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("ksa_bench", os.path.join(os.path.dirname(GOLDEN), "..", "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    st = {"Fft.Cur": np.arange(8.0), "Fft.Max": np.arange(8.0) + 1, "Fft.Min": np.arange(8.0) - 1, "Fft.Avg": np.full(8, np.nan),
+          "fftHM": np.ones((128, 4)), "hm_index": 3, "frames": 10}
+    out = bench.state_outputs(st)
+    assert sorted(out) == ["fft_avg", "fft_cur", "fft_hm", "fft_max", "fft_min"]
+    assert all(a.dtype == np.float32 for a in out.values()) and out["fft_hm"].shape == (128, 4)
+    rows = torch.arange(64 * 16, dtype=torch.float32).reshape(64, 16)
+    assert np.array_equal(bench.sample_frames(64, 16), np.arange(64))
+    assert np.array_equal(bench.take_rows(torch, rows, bench.sample_frames(64, 16)), rows.numpy())
+    monkeypatch.setattr(bench, "DUMP_ROWS_BYTES", 10 * 16 * 4)
+    idx = bench.sample_frames(64, 16)
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 64
+    assert np.array_equal(idx, bench.sample_frames(64, 16))
+    a = bench.take_rows(torch, rows, idx)
+    assert a.shape == (10, 16) and np.array_equal(a, rows.numpy()[idx])
+    bench.write_outputs(str(tmp_path / "d"), dict(out, rows=a))
+    for name, want in dict(out, rows=a).items():
+        assert np.array_equal(np.load(tmp_path / "d" / (name + ".npy")), want, equal_nan=True), name
+
+
 def test_tool_scripts_parse_and_are_listed():
     """Every script under tools/ parses (bash -n / py_compile) and has a row in tools/README.md -- the GPU box is the wrong
     place to find a syntax error, and an unlisted script is one nobody will find."""

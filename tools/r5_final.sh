@@ -14,10 +14,10 @@ if [ $what = tests ] || [ $what = all ]; then
   tail -3 $O/soak.log
 fi
 if [ $what = bench ] || [ $what = all ]; then
-  ( time timeout -k 10 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
+  ( time timeout -k 10 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
   grep real $O/bench_default.time; cut -c1-300 $O/bench_default.json
   for k in 2 3 4 5; do
-    timeout -k 10 400 python3 bench.py --config $k > $O/bench_c$k.json 2> $O/bench_c$k.err || echo "bench c$k failed"
+    timeout -k 10 400 python3 bench.py --config $k --full > $O/bench_c$k.json 2> $O/bench_c$k.err || echo "bench c$k failed"
     timeout -k 10 300 python3 bench.py --config $k --fmt u8 --no-cpu > $O/bench_c${k}_u8.json 2> $O/bench_c${k}_u8.err || echo "bench c$k u8 failed"
     python3 -c "
 import json

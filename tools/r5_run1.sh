@@ -50,7 +50,7 @@ for ln in sys.stdin:
   fi
 fi
 if [ $what = bench ] || [ $what = all ]; then
-  ( time timeout -k 10 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
+  ( time timeout -k 10 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
   grep real $O/bench_default.time; cut -c1-600 $O/bench_default.json
 fi
 echo r5_run1 $what done
