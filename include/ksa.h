@@ -24,9 +24,10 @@
 extern "C" {
 #endif
 
-#define KSA_ABI_VERSION 4 /* 2: ksa_set_adj takes its target; allreduce_state, host-pointer scan pass, sharded scan entries
+#define KSA_ABI_VERSION 5 /* 2: ksa_set_adj takes its target; allreduce_state, host-pointer scan pass, sharded scan entries
                              3: ksa_scan_spectra_dev, ksa_read_hm_rows, ksa_read_view; entry points restore the caller's current device
                              4: ksa_prof_clock
+                             5: ksa_frames_c64 / ksa_frames_u8 (zeroSpan batches from host memory)
                              A binding takes the number from ksa_abi_version() of the library it loaded, never from a literal. */
 #define KSA_HM_ROWS 128 /* waterfall history depth: maxHM K:448, fftHMMax K:611 */
 
@@ -103,6 +104,20 @@ int ksa_frames_dev(ksa_engine* e, const void* iq_dev, int32_t fmt, int64_t frame
 /* One block from host memory: the body of the reference's frame loop. */
 int ksa_frame_c64(ksa_engine* e, const float* iq_host);
 int ksa_frame_u8(ksa_engine* e, const uint8_t* iq_host);
+/* nframes capture blocks from HOST memory (pageable or pinned), [nframes][full_size] complex64 (re,im) or
+ * [nframes][2*full_size] uint8 I,Q: the same contract as ksa_frames_dev on a device copy of that memory with
+ * frame_stride = full_size, bit for bit (Cur/Max/Min/Avg, the ring, hm_index, frames_seen, the optional outputs and the
+ * commit = 0 partial / exchange block).  cur_db_host ([nframes][N]) and hm_rows_host ([nframes][hm_width]; refused when
+ * hm_width is 0) are optional.  1 <= nframes <= max_frames; every argument is checked before anything is enqueued, and a
+ * refused call leaves the engine as it was.  The blocks cross PCIe in slots of KSA_FRAME_SLOT_BYTES rounded down to a
+ * multiple of 4 whole blocks (at least 4 blocks), on an engine-owned copy stream that overlaps the next slot's copy with
+ * the transform of the one before; the first copy queues behind whatever the engine's stream holds.  Returns after the
+ * engine's stream is synchronised, like every host-pointer entry point. */
+#define KSA_FRAME_SLOT_BYTES (32ll << 20)
+int ksa_frames_c64(ksa_engine* e, const float* iq_host, int32_t nframes, int64_t first_index, int64_t total_frames,
+                   float* cur_db_host, float* hm_rows_host, int32_t commit);
+int ksa_frames_u8(ksa_engine* e, const uint8_t* iq_host, int32_t nframes, int64_t first_index, int64_t total_frames,
+                  float* cur_db_host, float* hm_rows_host, int32_t commit);
 /* zeroSpanPlay (K:547-564 feeding K:469-484): accumulate an already computed linear spectrum. */
 int ksa_frame_spectrum(ksa_engine* e, const float* mag_host /* [fft_size], fftshifted */);
 /* Partial block of the last ksa_frames_dev(commit=0): float[4][N] = {max, cur-or--inf, -min, sum}

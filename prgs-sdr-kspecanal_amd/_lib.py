@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # (A/B runs of variant builds swap the file: tools/with_lib.sh).
 LIB_PATH = os.path.join(HERE, "libksa.so")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 HM_ROWS = 128
 CUMU = {"RAW": 0, "AVG": 1, "MAX": 2, "MIN": 3}
 FMT_C64, FMT_U8 = 0, 1
@@ -49,6 +49,8 @@ SIGNATURES = {
     "ksa_frames_dev": (C.c_int, [_P, _P, _I32, _I64, _I32, _I64, _I64, _P, _P, _I32]),
     "ksa_frame_c64": (C.c_int, [_P, _P]),
     "ksa_frame_u8": (C.c_int, [_P, _P]),
+    "ksa_frames_c64": (C.c_int, [_P, _P, _I32, _I64, _I64, _P, _P, _I32]),
+    "ksa_frames_u8": (C.c_int, [_P, _P, _I32, _I64, _I64, _P, _P, _I32]),
     "ksa_frame_spectrum": (C.c_int, [_P, _P]),
     "ksa_partial_dev": (C.c_int, [_P, C.POINTER(_P)]),
     "ksa_commit": (C.c_int, [_P, _I64]),

@@ -124,6 +124,14 @@ struct ksa_engine {
   float* d_scan_send = nullptr;   // [nhalo][npasses][N] own bands packed for the right neighbours
   size_t scan_halo_cap = 0, scan_send_cap = 0;   // floats
   hipEvent_t ev_ready = nullptr, ev_copied = nullptr, ev_stream = nullptr;
+  // zeroSpan batches from host memory (ksa_frames_c64 / _u8): capture blocks cross PCIe slot by slot on copy_stream
+  hipStream_t copy_stream = nullptr;               // engine-owned, created on first use
+  void* d_slot[2] = {nullptr, nullptr};            // [slot frames][full_size] samples each
+  size_t slot_cap[2] = {0, 0};                     // bytes
+  hipEvent_t ev_slot_copied[2] = {nullptr, nullptr}, ev_slot_read[2] = {nullptr, nullptr}, ev_copy_start = nullptr;
+  float* d_host_rows = nullptr;                    // [nframes][hm_width] waterfall rows a host caller asked for
+  size_t host_rows_cap = 0;                        // floats
+  int plan_frames = 0;          // the spectrum launch in flight picks its shape for this many frames (>= its own nframes)
   // N > 16384: radix-16 / 32 / 64 decimation in frequency in front of the single-workgroup kernel (ksa_dif16.hpp)
   int sub_n = 0;                // size of the single-workgroup transform: fft_size (path 0) or fft_size/16 (path 2)
   float2* d_dif_tw = nullptr;   // [6][N1]
@@ -167,6 +175,10 @@ struct ksa_engine {
 namespace {
 
 using ksa::SpecParams;
+
+// The frame count a launch chooses its shape for (pair kernel, window split and its parts): the launch's own, or that of the
+// whole batch when a host batch arrives slot by slot (ksa_frames_c64 / _u8) -- every slot then gets the whole batch's plan.
+int plan_of(const ksa_engine* e, const SpecParams& p) { return std::max(p.nframes, e->plan_frames); }
 
 template <int N, int FMT, int RM, int CM>
 int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only);
@@ -223,7 +235,7 @@ int launch_spec_t(ksa_engine* e, const SpecParams& p, bool configure_only) {
         if (RM != 4 && launch_pair<N, FMT, 4>(e, p, true)) return 1;
         if (RM != 8 && launch_pair<N, FMT, 8>(e, p, true)) return 1;
         if (launch_pair<N, FMT, RM>(e, p, true)) return 1;
-      } else if (p.nframes >= 2 * e->num_cu * e->pair_bpc) return launch_pair<N, FMT, RM>(e, p, false);
+      } else if (plan_of(e, p) >= 2 * e->num_cu * e->pair_bpc) return launch_pair<N, FMT, RM>(e, p, false);
     }
   }
   // fold mode as a template constant (Tune<N>::fold_const) or as a run-time branch inside the window loop
@@ -265,8 +277,9 @@ int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
   // small batches (the per-frame drop-in, one scan pass): split every frame's windows over several
   // workgroups so that the GPU is filled; the partial folds are combined by a second, tiny kernel
   // (pays from N = 1024 up: 84 -> 51 us per block at N=4096, 720 -> 117 us at N=16384; tiny transforms only lose the launches)
-  if (e->d_parts && N >= 1024 && !exp_env("KSA_NO_SPLIT") && p.nwin > 1 && p.nframes * 2 <= capacity) {
-    q.parts = std::min(p.nwin, capacity / p.nframes);
+  const int plan = plan_of(e, p);
+  if (e->d_parts && N >= 1024 && !exp_env("KSA_NO_SPLIT") && p.nwin > 1 && plan * 2 <= capacity) {
+    q.parts = std::min(p.nwin, capacity / plan);
     q.part_out = e->d_parts;
   }
   const int grid = std::max(1, std::min(q.nframes * std::max(1, q.parts), capacity));
@@ -314,8 +327,9 @@ int launch_spec32_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
   }
   const int capacity = e->num_cu * e->blocks_per_cu;
   SpecParams q = p;
-  if (e->d_parts && !exp_env("KSA_NO_SPLIT") && p.nwin > 1 && p.nframes * 2 <= capacity) {   // window-split (latency) mode
-    q.parts = std::min(p.nwin, capacity / p.nframes);
+  const int plan = plan_of(e, p);
+  if (e->d_parts && !exp_env("KSA_NO_SPLIT") && p.nwin > 1 && plan * 2 <= capacity) {   // window-split (latency) mode
+    q.parts = std::min(p.nwin, capacity / plan);
     q.part_out = e->d_parts;
   }
   int grid = std::max(1, std::min(q.nframes * std::max(1, q.parts), capacity));
@@ -424,10 +438,15 @@ int prof_end(ksa_engine* e, hipEvent_t a, hipEvent_t b) {
 
 // N = 16 * N1 (32768 .. 262144): first stage in registers, N1-point stage by the single-workgroup kernel on the
 // 16 pseudo frames of every frame, interleave + dB + waterfall by dif16_finish_kernel (ksa_dif16.hpp).
-int run_dif16(ksa_engine* e, const SpecParams& p, int fmt) {
+// Chunks of dif_chunk frames are counted from frame 0 of the whole batch (this call holds its frames [batch_first,
+// batch_first + nframes) of batch_frames): a host batch that arrives slot by slot gets the chunks, and so the second-stage
+// plans, of one call over the whole batch.
+int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int batch_frames) {
   const int n = e->cfg.fft_size, n1 = e->sub_n, nwin = p.nwin;
-  for (int f0 = 0; f0 < p.nframes; f0 += e->dif_chunk) {
-    const int cf = std::min(e->dif_chunk, p.nframes - f0);
+  for (int f0 = 0, cf = 0; f0 < p.nframes; f0 += cf) {
+    const int g0 = batch_first + f0, chunk0 = g0 - g0 % e->dif_chunk;
+    const int chunk_frames = std::min(e->dif_chunk, batch_frames - chunk0);
+    cf = std::min(chunk0 + chunk_frames - g0, p.nframes - f0);
     ksa::DifParams a{};
     a.iq = p.iq;
     a.frame_stride = p.frame_stride;
@@ -466,6 +485,7 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt) {
     b.cumu = p.cumu;
     b.out_mode = ksa::OUT_LINEAR;
     b.out = e->d_dif_y;
+    e->plan_frames = chunk_frames * R;
     if (launch_spec_n<ksa::FMT_C64>(e, b, false)) return 1;
     ksa::DifFinishParams c{};
     c.y = e->d_dif_y;
@@ -495,8 +515,10 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt) {
 }
 
 // Spectrum stage for a batch: the single-workgroup LDS FFT, behind a radix-16 / 32 / 64 first stage for N > 16384.
+// The call transforms frames [batch_first, batch_first + nframes) of a batch of batch_frames (0: nframes) and takes the
+// whole batch's launch plan, ring rows and ring window: slot by slot it writes what one call over the batch writes.
 int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, int out_mode,
-                 float* out, bool with_hm, float* hm_rows) {
+                 float* out, bool with_hm, float* hm_rows, int batch_first = 0, int batch_frames = 0) {
   const ksa_config& c = e->cfg;
   if (fmt != KSA_FMT_C64 && fmt != KSA_FMT_U8) return fail("unknown sample format %d", fmt);
   if (nframes < 1 || nframes > c.max_frames) return fail("nframes %d outside 1..max_frames(%d)", nframes, c.max_frames);
@@ -533,8 +555,10 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   p.adj = with_hm ? e->d_adj : nullptr;
   p.hm_rows = with_hm ? hm_rows : nullptr;
   p.hm_ring = with_hm ? e->d_hm : nullptr;
-  p.hm_index0 = e->hm_index;
-  p.hm_first = std::max(0, nframes - KSA_HM_ROWS);
+  if (batch_frames < 1) batch_frames = nframes;
+  p.hm_index0 = (e->hm_index + batch_first) % KSA_HM_ROWS;
+  p.hm_first = std::max(0, batch_frames - KSA_HM_ROWS - batch_first);
+  e->plan_frames = batch_frames;
 #ifdef KSA_STAMPS
   static unsigned long long* dbg = nullptr;   // diagnostic build: 4096 blocks x 16 waves x 12 segments
   const size_t dbg_n = 4096 * 16 * 12;
@@ -549,11 +573,12 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   if (prof_begin(e, &ea, &eb)) return 1;
   int rc;
   if (e->path == 2) {
-    if ((rc = run_dif16(e, p, fmt))) return rc;
+    rc = run_dif16(e, p, fmt, batch_first, batch_frames);
   } else {
     rc = fmt == KSA_FMT_C64 ? launch_spec_n<ksa::FMT_C64>(e, p, false) : launch_spec_n<ksa::FMT_U8>(e, p, false);
-    if (rc) return rc;
   }
+  e->plan_frames = 0;
+  if (rc) return rc;
 #ifdef KSA_STAMPS
   if (const char* path = exp_env("KSA_STAMPS_FILE")) {
     hipStreamSynchronize(e->stream);
@@ -891,8 +916,11 @@ void ksa_destroy(ksa_engine* e) {
   hipSetDevice(e->cfg.device);
   hipDeviceSynchronize();
   for (auto& pr : e->prof_events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-  for (hipEvent_t ev : {e->ev_ready, e->ev_copied, e->ev_stream}) if (ev) hipEventDestroy(ev);
-  void* ptrs[] = {e->d_clk, e->d_gather, e->d_scan_stage, e->d_scan_rows, e->d_scan_halo, e->d_scan_send,
+  for (hipEvent_t ev : {e->ev_ready, e->ev_copied, e->ev_stream, e->ev_copy_start, e->ev_slot_copied[0], e->ev_slot_copied[1],
+                        e->ev_slot_read[0], e->ev_slot_read[1]})
+    if (ev) hipEventDestroy(ev);
+  if (e->copy_stream) hipStreamDestroy(e->copy_stream);
+  void* ptrs[] = {e->d_slot[0], e->d_slot[1], e->d_host_rows, e->d_clk, e->d_gather, e->d_scan_stage, e->d_scan_rows, e->d_scan_halo, e->d_scan_send,
                   e->d_starts, e->d_start_last, e->d_window, e->d_window32, e->d_tw_mid, e->d_tw_last, e->d_adj, e->d_scan_adj,
                   e->d_iq_stage, e->d_frames, e->d_part, e->d_xchg, e->d_state, e->d_scan_state, e->d_scan_hm,
                   e->d_levels, e->d_parts, e->d_highs, e->d_scan_avg_rows, e->d_dif_tw, e->d_dif_z, e->d_dif_y, e->d_ones, e->d_starts_b};
@@ -974,6 +1002,64 @@ static int frame_host(ksa_engine* e, const void* iq_host, int fmt) {
 
 int ksa_frame_c64(ksa_engine* e, const float* iq_host) { return frame_host(e, iq_host, KSA_FMT_C64); }
 int ksa_frame_u8(ksa_engine* e, const uint8_t* iq_host) { return frame_host(e, iq_host, KSA_FMT_U8); }
+
+// A batch from host memory.  Its blocks cross PCIe slot by slot (include/ksa.h: KSA_FRAME_SLOT_BYTES) on the engine's copy
+// stream into two device slots, while the engine's stream transforms the slot copied before; events order both ways (a slot's
+// transform waits for its copy, the next copy into a slot waits for the transform that read it).  Every slot runs with the whole
+// batch's launch plan and ring rows and writes its dB rows into d_frames at the batch position; ONE accumulate over the whole
+// batch follows the last slot.  That is ksa_frames_dev on a device copy of the batch, bit for bit.
+static int frames_host(ksa_engine* e, const void* iq_host, int fmt, int nframes, long long first_index, long long total,
+                       float* cur_db_host, float* hm_rows_host, int commit) {
+  if (!e || !iq_host) return fail("null argument");
+  const ksa_config& c = e->cfg;
+  if (nframes < 1 || nframes > c.max_frames) return fail("nframes %d outside 1..max_frames(%d)", nframes, c.max_frames);
+  if (first_index < 0 || first_index + nframes > total) return fail("batch [%lld,+%d) outside run of %lld frames", first_index, nframes, total);
+  if (hm_rows_host && !c.hm_width) return fail("hm_rows_host given, but the engine has no waterfall (hm_width 0)");
+  DeviceGuard dev_guard;
+  HIP_OK(hipSetDevice(c.device));
+  const size_t n = (size_t)c.fft_size, frame_bytes = (size_t)c.full_size * sample_bytes(fmt);
+  // whole frames, a multiple of 4 (even for the pair kernel, 16-byte aligned row offsets however narrow the waterfall), >= 4
+  const int slot_frames = (int)std::max<size_t>(4, (size_t)KSA_FRAME_SLOT_BYTES / frame_bytes / 4 * 4);
+  const size_t slot_bytes = (size_t)std::min(nframes, slot_frames) * frame_bytes;
+  // scratch, stream and events before the first enqueue: a refusal up to here leaves the engine as it was
+  for (int s = 0; s < 2; ++s)
+    if (ensure(reinterpret_cast<unsigned char**>(&e->d_slot[s]), &e->slot_cap[s], slot_bytes)) return 1;
+  if (hm_rows_host && ensure(&e->d_host_rows, &e->host_rows_cap, (size_t)nframes * c.hm_width)) return 1;
+  if (!e->copy_stream) HIP_OK(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
+  for (hipEvent_t* ev : {&e->ev_copy_start, &e->ev_slot_copied[0], &e->ev_slot_copied[1], &e->ev_slot_read[0], &e->ev_slot_read[1]})
+    if (!*ev) HIP_OK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  // the first copy queues behind whatever the engine's stream holds (ksa_set_stream contract)
+  HIP_OK(hipEventRecord(e->ev_copy_start, e->stream));
+  HIP_OK(hipStreamWaitEvent(e->copy_stream, e->ev_copy_start, 0));
+  float* const rows_dev = hm_rows_host ? e->d_host_rows : nullptr;
+  for (int f0 = 0, k = 0; f0 < nframes; f0 += slot_frames, ++k) {
+    const int nf = std::min(slot_frames, nframes - f0), s = k & 1;
+    if (k >= 2) HIP_OK(hipStreamWaitEvent(e->copy_stream, e->ev_slot_read[s], 0));
+    HIP_OK(hipMemcpyAsync(e->d_slot[s], static_cast<const unsigned char*>(iq_host) + (size_t)f0 * frame_bytes, (size_t)nf * frame_bytes,
+                          hipMemcpyHostToDevice, e->copy_stream));
+    HIP_OK(hipEventRecord(e->ev_slot_copied[s], e->copy_stream));
+    HIP_OK(hipStreamWaitEvent(e->stream, e->ev_slot_copied[s], 0));
+    if (run_spectrum(e, e->d_slot[s], fmt, c.full_size, nf, KSA_OUT_DB, e->d_frames + (size_t)f0 * n, c.hm_width > 0,
+                     rows_dev ? rows_dev + (size_t)f0 * c.hm_width : nullptr, f0, nframes)) return 1;
+    HIP_OK(hipEventRecord(e->ev_slot_read[s], e->stream));
+  }
+  if (run_accumulate(e, e->d_frames, nframes, first_index, total)) return 1;
+  e->pending_frames = nframes;
+  if (commit && do_commit(e, total, nframes)) return 1;
+  if (cur_db_host) HIP_OK(hipMemcpyAsync(cur_db_host, e->d_frames, (size_t)nframes * n * 4, hipMemcpyDeviceToHost, e->stream));
+  if (rows_dev) HIP_OK(hipMemcpyAsync(hm_rows_host, rows_dev, (size_t)nframes * c.hm_width * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int ksa_frames_c64(ksa_engine* e, const float* iq_host, int32_t nframes, int64_t first_index, int64_t total_frames,
+                   float* cur_db_host, float* hm_rows_host, int32_t commit) {
+  return frames_host(e, iq_host, KSA_FMT_C64, nframes, first_index, total_frames, cur_db_host, hm_rows_host, commit);
+}
+int ksa_frames_u8(ksa_engine* e, const uint8_t* iq_host, int32_t nframes, int64_t first_index, int64_t total_frames,
+                  float* cur_db_host, float* hm_rows_host, int32_t commit) {
+  return frames_host(e, iq_host, KSA_FMT_U8, nframes, first_index, total_frames, cur_db_host, hm_rows_host, commit);
+}
 
 int ksa_frame_spectrum(ksa_engine* e, const float* mag_host) {
   if (!e || !mag_host) return fail("null argument");

@@ -185,6 +185,25 @@ class SpectrumEngine:
         fn = lib.ksa_frame_u8 if fmt == FMT_U8 else lib.ksa_frame_c64
         check(fn(self._h, _ptr(a)))
 
+    def frames(self, blocks, first_index=0, total_frames=None, cur_db=False, hm_rows=False, commit=True):
+        """A batch of capture blocks from HOST memory in one call (ksa_frames_c64 / _u8): blocks = [k][fullSize] complex64 or
+        [k][2*fullSize] uint8 I,Q, a numpy array or PinnedBuffer.array (pinned memory copies faster).  The same state as
+        frames_dev on a device copy of the batch.  Returns (cur_db float32[k, N] or None, hm_rows float32[k, W] or None):
+        the per-frame dB spectra and waterfall rows, each when asked for."""
+        a = np.asarray(blocks)
+        if a.dtype == np.uint8:
+            a, fn, per = np.ascontiguousarray(a), lib.ksa_frames_u8, 2 * self.full_size
+        else:
+            a, fn, per = np.ascontiguousarray(a, dtype=np.complex64), lib.ksa_frames_c64, self.full_size
+        if a.ndim != 2 or a.shape[1] != per:
+            raise KsaError("frames wants [k][%d] %s, got %s" % (per, a.dtype, a.shape))
+        k = int(a.shape[0])
+        total = k if total_frames is None else int(total_frames)
+        db = np.empty((k, self.fft_size), dtype=np.float32) if cur_db else None
+        rows = np.empty((k, self.hm_width), dtype=np.float32) if hm_rows else None
+        check(fn(self._h, _ptr(a), k, int(first_index), total, _ptr(db), _ptr(rows), 1 if commit else 0))
+        return db, rows
+
     def frame_spectrum(self, mag):
         a = np.ascontiguousarray(mag, dtype=np.float32)
         if a.size != self.fft_size:

@@ -10,9 +10,11 @@ mode words and aliases (K:816, K:912-921), the defaults (K:41-59), the dict `d` 
 with the same key names, the module-level `sdr_curscan(d)` seam that playback rebinds (K:531, K:543), and the
 arrays handed to matplotlib: d['Fft.Cur'|'Fft.Max'|'Fft.Min'|'Fft.Avg'], the freqs axis, and the
 [128, W] waterfall buffer (K:470-481, K:729).  New keys are additive: `source` (rtlsdr|synth|file:<path>),
-`device`, `iqFormat` (c64|u8).  What moved to the GPU: everything from the IQ block to those arrays.
+`device`, `iqFormat` (c64|u8), `frameBatch` (zeroSpan blocks per device call, default 1).  What moved to the GPU:
+everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
-refreshed once per pass (the whole pass is one device call) instead of once per tuned band.
+refreshed once per pass (the whole pass is one device call) instead of once per tuned band, and in zeroSpan with
+frameBatch > 1 once per batch.
 Hand-off traffic: with a decimating pltCompress (AVG|MAX|MIN) a frame / pass brings back the four
 xRes-point Levels curves, the peak markers and the ONE new waterfall row (ksa_read_view, d['handoff.bytes']); the
 full-width d['Fft.*'] arrays are read from the device when a RAW / CONV plot needs them and once at the end of a run:
@@ -56,6 +58,7 @@ _KEYS = {
     "ZEROSPANSAVEFILE": ("zeroSpanSaveFile", str), "ZEROSPANPLAYFILE": ("zeroSpanPlayFile", str),
     # additive keys of this build
     "SOURCE": ("source", str), "DEVICE": ("device", int), "IQFORMAT": ("iqFormat", str.lower),
+    "FRAMEBATCH": ("frameBatch", int),
 }
 
 
@@ -70,7 +73,7 @@ def defaults():
         "SaveSigLvls": "", "AdjSigLvls": "", "bDataMin": True, "bDataMax": True, "bDataAvg": True, "bDataCur": True,
         "bGrid": True, "bUsePSD": False, "bScanRangeBaseDataIsRaw": False,
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
-        "source": "rtlsdr", "device": 0, "iqFormat": "c64", "cmd.stop": False,
+        "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "cmd.stop": False,
     }
 
 
@@ -142,6 +145,10 @@ def handle_args(d, argv=None):
                 break
     if d["curScanCumuMode"] not in ("AVG", "MAX", "MIN", "RAW"):
         prg_quit(d, "ERROR: Unknown cumuMode [{}], Quiting...".format(d["curScanCumuMode"]))
+    if d["frameBatch"] < 1:
+        prg_quit(d, "ERROR:handle_args: frameBatch [{}] must be >= 1".format(d["frameBatch"]))
+    if d["bUsePSD"] and d["frameBatch"] > 1:
+        prg_quit(d, "ERROR:handle_args: frameBatch [{}] needs bUsePSD false: the PSD diagnostic is per block".format(d["frameBatch"]))
     return d
 
 
@@ -157,7 +164,8 @@ def print_info(d):
         d["prgMode"], d["prgLoopCnt"], d["bPltLevels"], d["bPltHeatMap"]))
     print("INFO: xRes [{}], bGrid [{}], pltCompress [{}], pltCompressHM [{}]".format(
         d["xRes"], d["bGrid"], d["pltCompress"], d["pltCompressHM"]))
-    print("INFO: source [{}], device [{}], iqFormat [{}]".format(d["source"], d["device"], d["iqFormat"]))
+    print("INFO: source [{}], device [{}], iqFormat [{}], frameBatch [{}]".format(d["source"], d["device"], d["iqFormat"],
+                                                                                d["frameBatch"]))
 
 
 # ------------------------------------------------------------------------------------------ SDR seam
@@ -455,11 +463,12 @@ def _materialize(d, eng, scan=False):
     return st
 
 
-def _handoff(d, eng, freqs, scan=False):
+def _handoff(d, eng, freqs, scan=False, new_rows=1):
     """What one frame (zeroSpan, K:477-504) or one pass (scan, K:669-697 + K:729) hands to the plots.  With a
     decimating pltCompress everything is reduced on the device and ONE call (ksa_read_view) brings back the four
     xRes-point curves, the peak markers of the last plotted curve and the one new waterfall row: 4*xRes + xRes
-    floats instead of 4*N + 128*W.  RAW / CONV plots need the full curves and materialise them."""
+    floats instead of 4*N + 128*W.  RAW / CONV plots need the full curves and materialise them.  After a batch of
+    frames (frameBatch) the newest `new_rows` (<= 128) ring rows come back in the same call."""
     if not _view_on_device(d, len(freqs)):
         _materialize(d, eng, scan)
         _plot_heatmap(d, d["fftHM"])
@@ -479,10 +488,11 @@ def _handoff(d, eng, freqs, scan=False):
     delta = d["pltHighsDelta4Marking"] * (xs[-1] - xs[0])
     want_marks = last is not None and 1 <= count <= 64 and len(xs) > 1
     lv, idx, lvl, rows, hm_index = eng.view(d["xRes"], d["pltCompress"], curve=last if want_marks else None,
-                                            min_sep=delta / cell, count=count, hm_rows=1, scan=scan)
+                                            min_sep=delta / cell, count=count, hm_rows=new_rows, scan=scan)
     d["handoff.bytes"] = (lv.size + rows.size + 2 * len(idx)) * 4
     d["Levels"] = {"x": xs, "max": lv[1], "min": lv[2], "avg": lv[3], "cur": lv[0]}
-    d["fftHM"][(hm_index - 1) % _engine.HM_ROWS] = rows[0]               # the host copy of the ring takes the new row (K:480 / K:697)
+    for r in range(new_rows):                                             # the host copy of the ring takes the new rows (K:480 / K:697)
+        d["fftHM"][(hm_index - new_rows + r) % _engine.HM_ROWS] = rows[r]
     d["fftHMIndex"] = hm_index
     _plot_heatmap(d, d["fftHM"])
     drawing = d.get("plt") is not None and d["bPltLevels"]
@@ -555,9 +565,24 @@ def zero_span(d):
     freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], 1 / d["samplingRate"]) + d["centerFreq"])   # K:444-445
     d["freqs"] = freqs
     print("ZeroSpan: min[{}] max[{}]".format(min(freqs), max(freqs)))
-    eng = get_engine(d)
+    batch = d["frameBatch"]
+    if batch > 1 and sdr_curscan is not _gpu_curscan:
+        print("WARN:zero_span: frameBatch [{}] is ignored when playing saved spectra".format(batch))
+        batch = 1
+    eng = get_engine(d, max_frames=batch)
     eng.reset()
     d["fftHM"], d["fftHMIndex"] = np.zeros((_engine.HM_ROWS, eng.hm_width)), 0     # K:456; the device ring starts the same
+    if batch > 1:
+        _zero_span_batches(d, eng, freqs, batch)
+    else:
+        _zero_span_frames(d, eng, freqs)
+    if _materialize(d, eng)["frames"] == 0:      # full-width arrays once, for SaveSigLvls and whoever called main()
+        for k in ("Fft.Max", "Fft.Min", "Fft.Avg", "Fft.Cur"):
+            d[k] = None                          # no frame ran: the curves are still None (K:427-430)
+
+
+def _zero_span_frames(d, eng, freqs):
+    """frameBatch 1: the reference's loop, one block per pass."""
     prev = time.time()
     for i in range(d["prgLoopCnt"]):
         now = time.time()
@@ -580,9 +605,46 @@ def zero_span(d):
         if d["cmd.stop"]:
             break
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
-    if _materialize(d, eng)["frames"] == 0:      # full-width arrays once, for SaveSigLvls and whoever called main()
-        for k in ("Fft.Max", "Fft.Min", "Fft.Avg", "Fft.Cur"):
-            d[k] = None                          # no frame ran: the curves are still None (K:427-430)
+
+
+def _zero_span_batches(d, eng, freqs, batch):
+    """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
+    (ksa_frames_c64 / _u8); flags, the progress line and the plot refresh come once per batch.  prgLoopCnt still counts
+    frames, and a source that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of
+    frameBatch 1."""
+    u8 = d.get("iqFormat") == "u8" and hasattr(d["sdr"], "read_bytes")      # what sdr_read(..., raw) delivers
+    full = d["fullSize"]
+    stage = _engine.PinnedBuffer((batch, 2 * full) if u8 else (batch, full), np.uint8 if u8 else np.complex64)
+    blocks = stage.array
+    read_blocks = getattr(d["sdr"], "read_blocks", None)
+    try:
+        done, prev = 0, time.time()
+        while done < d["prgLoopCnt"]:
+            k = min(batch, d["prgLoopCnt"] - done)
+            now = time.time()
+            print("ZeroSpan:{}:{}".format(done, now - prev))
+            prev = now
+            eng.set_flags(d["bDataMax"], d["bDataMin"], d["bDataAvg"])      # GUI toggles K:471-476, once per batch
+            if read_blocks is not None:
+                got = read_blocks(k, full, u8, blocks)
+            else:
+                got = 0
+                try:
+                    while got < k:
+                        blocks[got] = sdr_read(d["sdr"], full, raw=u8)
+                        got += 1
+                except EOFError:
+                    pass
+            if got:
+                eng.frames(blocks[:got])                                     # K:464-484 for the whole batch, one call
+            done += got
+            if got < k:
+                prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)
+            if d["cmd.stop"]:
+                break
+            _handoff(d, eng, freqs, new_rows=min(got, _engine.HM_ROWS))     # once per batch: the batch's newest rows
+    finally:
+        stage.close()
 
 
 def zero_span_save(d):

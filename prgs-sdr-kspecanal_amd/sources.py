@@ -88,3 +88,40 @@ class FileSdr(_SdrBase):
     def read_samples(self, n):
         b = self.read_bytes(2 * int(n)).astype(np.float64)
         return (b[0::2] - 127.5) / 127.5 + 1j * ((b[1::2] - 127.5) / 127.5)
+
+    @staticmethod
+    def _unpack(b):
+        b = b.astype(np.float64)
+        return (b[..., 0::2] - 127.5) / 127.5 + 1j * ((b[..., 1::2] - 127.5) / 127.5)
+
+    def read_blocks(self, k, length, raw, out):
+        """Fill out[:k] exactly as k calls of kspecanal.sdr_read(self, length, raw) would: the same bytes consumed (reads of at
+        most 2^18 samples, a short tail read rounded up to a power of two and cut back, K:343) and the same values (uint8 I,Q, or
+        complex64 through read_samples' unpack).  Returns the number of whole blocks read before the end of the capture."""
+        k, length = int(k), int(length)
+        unit = 2 ** 18                                     # kspecanal.SDR_READ_UNIT, K:311
+        parts = [unit] * (length // unit) + ([length % unit] if length % unit else [])
+        wants = [n if n >= unit else int(2 ** np.ceil(np.log2(n))) for n in parts]
+        per = 2 * sum(wants)                               # bytes one block consumes
+        done = 0
+        if per == 2 * length and not self.loop:
+            # every read is used whole: the blocks are back to back in the capture, one slice per group of blocks
+            whole = min(k, (len(self._raw) - self._pos) // per)
+            for g in range(0, whole, 64):
+                m = min(64, whole - g)
+                src = self._raw[self._pos:self._pos + m * per].reshape(m, per)
+                out[g:g + m] = src if raw else self._unpack(src)
+                self._pos += m * per
+            done = whole
+        for i in range(done, k):                          # read by read, as sdr_read does (end of file, loop)
+            try:
+                col = 0
+                for n, want in zip(parts, wants):
+                    if raw:
+                        out[i, 2 * col:2 * (col + n)] = self.read_bytes(2 * want)[:2 * n]
+                    else:
+                        out[i, col:col + n] = self.read_samples(want)[:n]
+                    col += n
+            except EOFError:
+                return i
+        return k
