@@ -48,7 +48,9 @@ typedef struct ksa_engine ksa_engine;
 typedef struct ksa_config {
   int32_t abi_version;          /* KSA_ABI_VERSION */
   int32_t device;               /* HIP device ordinal */
-  int32_t fft_size;             /* d['fftSize']: power of two, 16 .. 1048576 */
+  int32_t fft_size;             /* d['fftSize']: power of two, 16 .. 1048576; or 2^a*3^b*5^c, a multiple of 4, 16 .. 16384
+                                   (the mixed-radix path; the layout and the calls are unchanged, so the ABI number is too:
+                                   a library without that path refuses such sizes in ksa_create) */
   int32_t full_size;            /* d['fullSize'] K:926-929: samples per captured block */
   int32_t num_windows;          /* windows actually transformed (K:385-390) */
   const int32_t* window_starts; /* host[num_windows]: iStart = int(i*fftSize*nonOverlap) K:386 */
@@ -57,7 +59,7 @@ typedef struct ksa_config {
   int32_t cumu_mode;            /* KSA_CUMU_*: within-block fold K:392-395 */
   float gain;                   /* d['gain'] subtracted by LogNoGain K:109 */
   float min_amp;                /* d['minAmp4Clip'] K:53, K:101 */
-  int32_t hm_width;             /* d['PltHeatMapWidth'] K:449-455 (zeroSpan) ; must divide fft_size */
+  int32_t hm_width;             /* d['PltHeatMapWidth'] K:449-455 (zeroSpan) ; must divide fft_size (a power of two when fft_size is one) */
   int32_t max_frames;           /* largest batch handed to ksa_frames_dev / ksa_curscan_dev / steps per scan pass */
   float u8_offset, u8_scale;    /* uint8 unpack (b - offset) / scale; 127.5 / 127.5 by default */
   /* scan mode (0 = zeroSpan only): _scan_range K:568-698 */
@@ -274,7 +276,9 @@ int ksa_kernel_info(ksa_engine* e, int32_t* threads, int32_t* lds_bytes, int32_t
                                                     batches run two frames per workgroup in packed fp32 (lds / vgprs /
                                                     grid then describe that kernel), small ones the path-0 kernel;
                                                     5 = N = 64: complex64 input runs the 8 x 8 plan with adjacent-sample
-                                                    loads (lds / vgprs / grid describe it), uint8 input the path-0 kernel */);
+                                                    loads (lds / vgprs / grid describe it), uint8 input the path-0 kernel;
+                                                    6 = N = 2^a*3^b*5^c (not a power of two): the mixed-radix LDS FFT,
+                                                    one frame per workgroup, threads chosen per N */);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@
 #include "ksa_kernels32.hpp"
 #include "ksa_kernels64.hpp"
 #include "ksa_kernels_pair.hpp"
+#include "ksa_kernels_mr.hpp"
 
 namespace {
 
@@ -40,6 +41,16 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+
+// fft_size of the mixed-radix path (6): 2^a * 3^b * 5^c, a multiple of 4 (float4 rows), 16 .. 16384 (one transform in LDS),
+// not a power of two (those keep their own plans)
+bool is_mixed_radix(int n) {
+  if (n < 16 || n > 16384 || n % 4 || is_pow2(n)) return false;
+  int m = n;
+  for (int f : {2, 3, 5})
+    while (m % f == 0) m /= f;
+  return m == 1;
+}
 
 // Entry points run on their engine's device and hand the caller's current device back on every exit path (a process that
 // drives one engine per GPU, or torch beside libksa, keeps its own notion of "current").
@@ -162,6 +173,8 @@ struct ksa_engine {
   bool k64_ok = false;
   bool win_ones = false;          // every tap of the window table is exactly 1.0f (the reference's default window, K:52)
   int k64_bpc = 0, k64_vgprs = 0;
+  // path 6: fft_size 2^a * 3^b * 5^c (ksa_kernels_mr.hpp); the plan's twiddles live in d_tw_mid
+  ksa::MrPlan mr{};
   // profiling
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -421,6 +434,75 @@ int launch_spec_n(ksa_engine* e, const SpecParams& p, bool cfg_only) {
   }
 }
 
+// fft_size 2^a * 3^b * 5^c (path 6): the mixed-radix kernel, one frame per workgroup at the plan's thread count.  It has no
+// window split (p.parts): a one-frame batch runs on one workgroup.
+template <int FMT>
+int launch_mr(ksa_engine* e, const SpecParams& p, bool configure_only) {
+  auto kfn = ksa::mixed_radix_kernel<FMT>;
+  const int lds_bytes = e->mr.n * (int)sizeof(float2);
+  if (configure_only) {
+    // (one kernel serves every N of the path: its attribute is set to the largest transform, not to this engine's)
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * (int)sizeof(float2)));
+    hipFuncAttributes attr;
+    HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
+    int occ = 0;
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, e->threads, lds_bytes));
+    if (FMT == ksa::FMT_C64) {
+      e->lds_bytes = lds_bytes;
+      e->vgprs = attr.numRegs;
+      e->blocks_per_cu = std::max(1, occ);
+    }
+    return 0;
+  }
+  const int grid = std::max(1, std::min(p.nframes, e->num_cu * e->blocks_per_cu));
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(e->threads), lds_bytes, e->stream, p, e->mr);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// Plan of path 6: radix-5 passes, radix-3 passes, radix-4 passes, one radix-2 pass if the power of two is odd, and the radix-4
+// pass that every plan ends with (N % 4 == 0).  Twiddles in double, stored as float: pass s with ns = product of the radices
+// before it holds [R-1][ns] = W_(ns*R)^(r*k), r = 1..R-1, k < ns.  Threads: the fewest (a multiple of 64) that keep every
+// pass at ceil(N / (R*T)) <= MrNb<R> butterflies per thread.
+int plan_mr(int n, ksa::MrPlan* plan, int* threads, std::vector<float2>* tw) {
+  int m = n / 4, a = 0, b = 0, c = 0;
+  while (m % 2 == 0) { m /= 2; ++a; }
+  while (m % 3 == 0) { m /= 3; ++b; }
+  while (m % 5 == 0) { m /= 5; ++c; }
+  if (m != 1) return fail("fft_size %d is not 4 * 2^a * 3^b * 5^c", n);
+  std::vector<int> r;
+  r.insert(r.end(), c, 5);
+  r.insert(r.end(), b, 3);
+  r.insert(r.end(), a / 2, 4);
+  if (a % 2) r.push_back(2);
+  r.push_back(4);
+  if ((int)r.size() > ksa::MR_MAX_PASSES) return fail("fft_size %d needs %zu passes (> %d)", n, r.size(), ksa::MR_MAX_PASSES);
+  *plan = ksa::MrPlan{};
+  plan->n = n;
+  plan->npass = (int)r.size();
+  tw->clear();
+  int ns = 1;
+  for (int s = 0; s < plan->npass; ++s) {
+    const int R = r[s];
+    plan->radix[s] = R;
+    plan->tw_off[s] = (int)tw->size();
+    if (s > 0)
+      for (int q = 1; q < R; ++q)
+        for (int k = 0; k < ns; ++k) {
+          const double ang = -2.0 * M_PI * (double)q * (double)k / ((double)ns * R);
+          tw->push_back(make_float2((float)std::cos(ang), (float)std::sin(ang)));
+        }
+    ns *= R;
+  }
+  auto nb = [](int R) { return R == 2 ? 8 : R == 3 ? 6 : 4; };    // ksa::MrNb<R>
+  for (int t = 64; t <= ksa::MR_MAX_THREADS; t += 64) {
+    bool fits = true;
+    for (int R : r) fits &= (n / R + t - 1) / t <= nb(R);
+    if (fits) { *threads = t; return 0; }
+  }
+  return fail("fft_size %d needs more than %d threads", n, ksa::MR_MAX_THREADS);
+}
+
 int prof_begin(ksa_engine* e, hipEvent_t* a, hipEvent_t* b) {
   *a = *b = nullptr;
   if (!e->prof || e->prof_events.size() >= 8192) return 0;
@@ -574,6 +656,8 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   int rc;
   if (e->path == 2) {
     rc = run_dif16(e, p, fmt, batch_first, batch_frames);
+  } else if (e->path == 6) {
+    rc = fmt == KSA_FMT_C64 ? launch_mr<ksa::FMT_C64>(e, p, false) : launch_mr<ksa::FMT_U8>(e, p, false);
   } else {
     rc = fmt == KSA_FMT_C64 ? launch_spec_n<ksa::FMT_C64>(e, p, false) : launch_spec_n<ksa::FMT_U8>(e, p, false);
   }
@@ -704,14 +788,18 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   *out = nullptr;
   if (cfg->abi_version != KSA_ABI_VERSION) return fail("ABI version %d, library is %d", cfg->abi_version, KSA_ABI_VERSION);
   const int n = cfg->fft_size;
-  if (!is_pow2(n) || n < 16 || n > (1 << 20)) return fail("fft_size %d must be a power of two in 16..1048576", n);
+  const bool mixed = is_mixed_radix(n);
+  if (!mixed && (!is_pow2(n) || n < 16 || n > (1 << 20)))
+    return fail("fft_size %d must be a power of two in 16..1048576, or 2^a*3^b*5^c, a multiple of 4, in 16..16384", n);
   if (cfg->full_size < n) return fail("full_size %d < fft_size %d", cfg->full_size, n);
   if (cfg->num_windows < 1 || !cfg->window_starts || !cfg->window) return fail("window table / starts missing");
   for (int i = 0; i < cfg->num_windows; ++i)
     if (cfg->window_starts[i] < 0 || cfg->window_starts[i] + n > cfg->full_size)
       return fail("window %d start %d runs past the block", i, cfg->window_starts[i]);
   if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_MIN) return fail("unknown cumu_mode %d", cfg->cumu_mode);
-  if (cfg->hm_width < 0 || (cfg->hm_width && (n % cfg->hm_width || !is_pow2(cfg->hm_width))))
+  if (mixed && (cfg->hm_width < 0 || (cfg->hm_width && n % cfg->hm_width)))
+    return fail("hm_width %d must divide fft_size %d", cfg->hm_width, n);
+  if (!mixed && (cfg->hm_width < 0 || (cfg->hm_width && (n % cfg->hm_width || !is_pow2(cfg->hm_width)))))
     return fail("hm_width %d must be a power of two dividing fft_size", cfg->hm_width);
   if (cfg->max_frames < 1) return fail("max_frames must be >= 1");
   if (!(cfg->u8_scale != 0.f)) return fail("u8_scale must be non-zero");
@@ -741,7 +829,17 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   if ((rc = upload(&e->d_window, cfg->window, (size_t)n))) return bail(rc);
   e->win_ones = std::all_of(cfg->window, cfg->window + n, [](float w) { return w == 1.0f; });
 
-  {
+  if (mixed) {
+    e->path = 6;
+    e->sub_n = n;
+    std::vector<float2> tw;
+    if ((rc = plan_mr(n, &e->mr, &e->threads, &tw))) return bail(rc);
+    if ((rc = upload(&e->d_tw_mid, tw.data(), tw.size()))) return bail(rc);
+    e->mr.tw = e->d_tw_mid;
+    SpecParams dummy{};
+    if ((rc = launch_mr<ksa::FMT_C64>(e, dummy, true))) return bail(rc);
+    if ((rc = launch_mr<ksa::FMT_U8>(e, dummy, true))) return bail(rc);
+  } else {
     e->path = n <= 16384 ? 0 : 2;
     e->dif_radix = n <= 262144 ? 16 : n == 524288 ? 32 : 64;
     const int sn = e->path == 0 ? n : n / e->dif_radix;     // the single-workgroup transform
@@ -897,7 +995,7 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   e->d_partial = e->d_xchg;
   if (cfg->hm_width) e->d_hm = e->d_xchg + 4 * nn;
   ALLOC(e->d_state, 4 * nn * 4);
-  ALLOC(e->d_parts, (size_t)e->num_cu * e->blocks_per_cu * (size_t)e->sub_n * 4);
+  if (e->path != 6) ALLOC(e->d_parts, (size_t)e->num_cu * e->blocks_per_cu * (size_t)e->sub_n * 4);   // (path 6 has no window split)
   if (cfg->scan_total_entries) {
     ALLOC(e->d_scan_state, (size_t)4 * cfg->scan_total_entries * 4);
     ALLOC(e->d_scan_hm, (size_t)KSA_HM_ROWS * cfg->scan_hm_width * 4);

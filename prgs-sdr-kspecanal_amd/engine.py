@@ -16,6 +16,28 @@ MIN_AMP_DEFAULT = (1 / 256) * 0.00001   # gMinAmp4Clip K:53
 FFT2FULL_LESS, FFT2FULL_MORE = 8, 2     # K:49-50
 
 
+FFT_SIZE_RULE = ("fftSize must be a power of two in 16..1048576, or 2^a*3^b*5^c that is a multiple of 4 in 16..16384 "
+                 "(mixed-radix path)")
+
+
+def fft_size_supported(n):
+    """The fftSize values the engine transforms: every power of two 16..2^20 (K:391's numpy.fft.fft at the sizes the
+    reference's README asks for, README.rst:413-414), and N = 2^a*3^b*5^c, N % 4 == 0, 16 <= N <= 16384 (path 6)."""
+    n = int(n)
+    if 16 <= n <= 1 << 20 and n & (n - 1) == 0:
+        return True
+    if n < 16 or n > 16384 or n % 4:
+        return False
+    for f in (2, 3, 5):
+        while n % f == 0:
+            n //= f
+    return n == 1
+
+
+def fft_size_message(n):
+    return "fftSize %d is not supported: %s" % (int(n), FFT_SIZE_RULE)
+
+
 def full_size_for(fft_size, sampling_rate):
     """K:926-929."""
     return fft_size * FFT2FULL_LESS if fft_size < (sampling_rate // 8) else fft_size * FFT2FULL_MORE
@@ -84,6 +106,8 @@ class SpectrumEngine:
                  scan_total_entries=0, scan_non_overlap=0.5, scan_xres=None,
                  u8_offset=127.5, u8_scale=127.5, stream=None):
         self.fft_size = int(fft_size)
+        if not fft_size_supported(self.fft_size):
+            raise KsaError(fft_size_message(self.fft_size))
         self.full_size = int(full_size) if full_size is not None else full_size_for(self.fft_size, sampling_rate)
         self.non_overlap = float(non_overlap)
         self.cumu_mode = cumu_mode.upper()

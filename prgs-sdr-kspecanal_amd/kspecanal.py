@@ -143,6 +143,8 @@ def handle_args(d, argv=None):
                 print("WARN:fftSize[{}] NotMultipleOf xRes[{}], setting xRes to {}".format(d["fftSize"], d["xRes"], new))
                 d["xRes"] = new
                 break
+    if not _engine.fft_size_supported(d["fftSize"]):             # the engine's sizes (the reference takes any, K:391)
+        prg_quit(d, "ERROR:handle_args: " + _engine.fft_size_message(d["fftSize"]))
     if d["curScanCumuMode"] not in ("AVG", "MAX", "MIN", "RAW"):
         prg_quit(d, "ERROR: Unknown cumuMode [{}], Quiting...".format(d["curScanCumuMode"]))
     if d["frameBatch"] < 1:

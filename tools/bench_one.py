@@ -11,7 +11,8 @@ distinct = min(frames, max(1, (64 << 20) // (full * 8)))
 host = orc.synth_iq(full * distinct, 1 + n).astype(np.complex64)
 tile = torch.view_as_real(torch.from_numpy(host)).reshape(distinct, full, 2).cuda()
 iq = tile.repeat((frames + distinct - 1) // distinct, 1, 1)[:frames].contiguous()
-eng = ksa.SpectrumEngine(n, full_size=full, non_overlap=q, window=win, max_frames=frames, stream=torch.cuda.current_stream().cuda_stream)
+# (xres = N: any fftSize, 2^a*3^b*5^c included, has a valid waterfall width; curscan_dev writes no waterfall)
+eng = ksa.SpectrumEngine(n, full_size=full, non_overlap=q, window=win, xres=n, max_frames=frames, stream=torch.cuda.current_stream().cuda_stream)
 out = torch.empty((frames, n), dtype=torch.float32, device="cuda")
 for _ in range(2): eng.curscan_dev(iq, ksa.FMT_C64, frames, out, out_mode=ksa.OUT_DB)
 torch.cuda.synchronize(); eng.prof_enable(True)
