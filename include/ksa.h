@@ -33,6 +33,17 @@ extern "C" {
 
 /* d['curScanCumuMode'] K:31-34, K:58, consumed by data_cumu K:124-147 */
 enum { KSA_CUMU_RAW = 0, KSA_CUMU_AVG = 1, KSA_CUMU_MAX = 2, KSA_CUMU_MIN = 3 };
+/* Welch power spectral density (the reference's bUsePSD true, K:374-384, as a fold of this engine).  Per captured block
+ *   out[bin] = mag_scale * sum over k < num_windows of |FFT(x[start_k : start_k + N] * window)[bin]|^2     (fftshifted)
+ * with window_starts, window and mag_scale taken from the config as for the other folds: the caller chooses segmentation and
+ * scale.  matplotlib's (mlab.psd, two-sided, no detrend): start_k = k*(N - noverlap), num_windows = (full_size - noverlap) /
+ * (N - noverlap), mag_scale = 1 / (Fs * sum(window^2) * num_windows), Fs = 2 (plt.psd's default, which K:381 keeps).
+ * KSA_OUT_LINEAR returns that power; KSA_OUT_DB / KSA_OUT_DB_CLIP apply LogNoGain / Clip2MinAmp to it unchanged
+ * (10*log10(P) - gain, K:109 -- what the reference does to its PSD).  It is a mean: a NaN sample makes the bins it reaches NaN;
+ * an all-zero block gives -inf dB (KSA_OUT_DB) or 0 (KSA_OUT_DB_CLIP, min_amp 0) as with the other folds.  Every entry point
+ * that runs the spectrum stage accepts it.  The layout and the calls are unchanged, so the ABI number is too: a library
+ * without this fold refuses it in ksa_create ("unknown cumu_mode 4"). */
+enum { KSA_CUMU_PSD = 4 };
 /* IQ sample formats: complex64 (what sdr.read_samples hands over, narrowed from K:335's complex128)
  * and the dongle's native interleaved uint8 I,Q (pyrtlsdr packed_bytes_to_iq; K:301, K:339, K:346) */
 enum { KSA_FMT_C64 = 0, KSA_FMT_U8 = 1 };

@@ -5,8 +5,8 @@ the library and raises if it is missing: there is no CPU path in the product.
 """
 from ._lib import KsaError, lib, LIB_PATH, FMT_C64, FMT_U8, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS
 from .engine import (SpectrumEngine, PinnedBuffer, allreduce_state, scan_allstitch, scan_gather_state, full_size_for,
-                     window_starts, window_table, heatmap_width, fft_size_supported)
+                     window_starts, window_table, heatmap_width, fft_size_supported, psd_window_starts, psd_mag_scale)
 
 __all__ = ["KsaError", "SpectrumEngine", "lib", "LIB_PATH", "FMT_C64", "FMT_U8", "OUT_LINEAR", "OUT_DB",
            "OUT_DB_CLIP", "HM_ROWS", "PinnedBuffer", "allreduce_state", "scan_allstitch", "scan_gather_state", "full_size_for", "window_starts", "window_table", "heatmap_width",
-           "fft_size_supported"]
+           "fft_size_supported", "psd_window_starts", "psd_mag_scale"]

@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(HERE, "libksa.so")
 
 ABI_VERSION = 5
 HM_ROWS = 128
-CUMU = {"RAW": 0, "AVG": 1, "MAX": 2, "MIN": 3}
+CUMU = {"RAW": 0, "AVG": 1, "MAX": 2, "MIN": 3, "PSD": 4}
 FMT_C64, FMT_U8 = 0, 1
 OUT_LINEAR, OUT_DB, OUT_DB_CLIP = 0, 1, 2
 

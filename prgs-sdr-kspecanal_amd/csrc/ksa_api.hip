@@ -193,6 +193,10 @@ using ksa::SpecParams;
 // whole batch when a host batch arrives slot by slot (ksa_frames_c64 / _u8) -- every slot then gets the whole batch's plan.
 int plan_of(const ksa_engine* e, const SpecParams& p) { return std::max(p.nframes, e->plan_frames); }
 
+// KSA_CUMU_PSD engines run the CUMU_PSD instantiation of every spectrum kernel (a template constant everywhere, also where the
+// other folds branch at run time) with SpecParams::cumu = CUMU_AVG: the combines and the output stage of the two are the same.
+bool fold_psd(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PSD; }
+
 template <int N, int FMT, int RM, int CM>
 int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only);
 
@@ -206,7 +210,7 @@ int launch_pair_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
     HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
     int occ = 0;
     HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, ksa::Plan<N>::T, PP::LDS_BYTES));
-    if (FMT == ksa::FMT_C64 && CM == ksa::CUMU_AVG) {
+    if (FMT == ksa::FMT_C64 && (CM == ksa::CUMU_AVG || CM == ksa::CUMU_PSD)) {
       e->pair_bpc = std::max(1, occ);
       e->pair_vgprs = attr.numRegs;
       e->pair_lds = PP::LDS_BYTES;
@@ -222,6 +226,7 @@ int launch_pair_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
 
 template <int N, int FMT, int RM>
 int launch_pair(ksa_engine* e, const SpecParams& p, bool cfg_only) {
+  if (fold_psd(e)) return launch_pair_c<N, FMT, RM, ksa::CUMU_PSD>(e, p, cfg_only);
   if (cfg_only) {
     if (launch_pair_c<N, FMT, RM, ksa::CUMU_MAX>(e, p, true) || launch_pair_c<N, FMT, RM, ksa::CUMU_MIN>(e, p, true)) return 1;
     return launch_pair_c<N, FMT, RM, ksa::CUMU_AVG>(e, p, true);
@@ -251,6 +256,7 @@ int launch_spec_t(ksa_engine* e, const SpecParams& p, bool configure_only) {
       } else if (plan_of(e, p) >= 2 * e->num_cu * e->pair_bpc) return launch_pair<N, FMT, RM>(e, p, false);
     }
   }
+  if (fold_psd(e)) return launch_spec_c<N, FMT, RM, ksa::CUMU_PSD>(e, p, configure_only);
   // fold mode as a template constant (Tune<N>::fold_const) or as a run-time branch inside the window loop
   if constexpr (ksa::Tune<N>::fold_const(RM)) {
     if (configure_only) {
@@ -330,7 +336,7 @@ int launch_spec32_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
     HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
     int occ = 0;
     HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, P::T, P::LDS_BYTES));
-    if (FMT == ksa::FMT_C64 && CM == ksa::CUMU_AVG) {
+    if (FMT == ksa::FMT_C64 && (CM == ksa::CUMU_AVG || CM == ksa::CUMU_PSD)) {
       e->threads = P::T;
       e->lds_bytes = P::LDS_BYTES;
       e->vgprs = attr.numRegs;
@@ -359,6 +365,7 @@ int launch_spec32_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
 
 template <int N, int FMT>
 int launch_spec32(ksa_engine* e, const SpecParams& p, bool cfg_only) {
+  if (fold_psd(e)) return launch_spec32_c<N, FMT, ksa::CUMU_PSD>(e, p, cfg_only);
   if (cfg_only) {
     if (launch_spec32_c<N, FMT, ksa::CUMU_MAX>(e, p, true) || launch_spec32_c<N, FMT, ksa::CUMU_MIN>(e, p, true)) return 1;
     return launch_spec32_c<N, FMT, ksa::CUMU_AVG>(e, p, true);
@@ -376,7 +383,7 @@ int launch_spec64_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
     HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, ksa::Plan64::LDS_BYTES));
     int occ = 0;
     HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, ksa::Plan64::T, ksa::Plan64::LDS_BYTES));
-    if (CM == ksa::CUMU_AVG) {
+    if (CM == ksa::CUMU_AVG || CM == ksa::CUMU_PSD) {
       hipFuncAttributes attr;
       HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
       e->k64_bpc = std::max(1, occ);
@@ -392,6 +399,7 @@ int launch_spec64_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
 
 template <bool W1>
 int launch_spec64_w(ksa_engine* e, const SpecParams& p, bool cfg_only) {
+  if (fold_psd(e)) return launch_spec64_c<ksa::CUMU_PSD, W1>(e, p, cfg_only);
   if (cfg_only) {
     if (launch_spec64_c<ksa::CUMU_MAX, W1>(e, p, true) || launch_spec64_c<ksa::CUMU_MIN, W1>(e, p, true)) return 1;
     return launch_spec64_c<ksa::CUMU_AVG, W1>(e, p, true);
@@ -436,9 +444,12 @@ int launch_spec_n(ksa_engine* e, const SpecParams& p, bool cfg_only) {
 
 // fft_size 2^a * 3^b * 5^c (path 6): the mixed-radix kernel, one frame per workgroup at the plan's thread count.  It has no
 // window split (p.parts): a one-frame batch runs on one workgroup.
-template <int FMT>
+template <int FMT, bool PSD = false>
 int launch_mr(ksa_engine* e, const SpecParams& p, bool configure_only) {
-  auto kfn = ksa::mixed_radix_kernel<FMT>;
+  if constexpr (!PSD) {
+    if (fold_psd(e)) return launch_mr<FMT, true>(e, p, configure_only);
+  }
+  auto kfn = PSD ? ksa::mixed_radix_psd_kernel<FMT> : ksa::mixed_radix_kernel<FMT>;
   const int lds_bytes = e->mr.n * (int)sizeof(float2);
   if (configure_only) {
     // (one kernel serves every N of the path: its attribute is set to the largest transform, not to this engine's)
@@ -626,7 +637,7 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   p.tw_mid = e->d_tw_mid;
   p.tw_last = e->d_tw_last;
   p.scale = (float)c.mag_scale;
-  p.cumu = (raw || c.cumu_mode == KSA_CUMU_AVG) ? ksa::CUMU_AVG : c.cumu_mode == KSA_CUMU_MAX ? ksa::CUMU_MAX : ksa::CUMU_MIN;
+  p.cumu = (raw || c.cumu_mode == KSA_CUMU_AVG || c.cumu_mode == KSA_CUMU_PSD) ? ksa::CUMU_AVG : c.cumu_mode == KSA_CUMU_MAX ? ksa::CUMU_MAX : ksa::CUMU_MIN;
   p.out_mode = out_mode;
   p.gain = c.gain;
   p.min_amp = c.min_amp;
@@ -796,7 +807,7 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   for (int i = 0; i < cfg->num_windows; ++i)
     if (cfg->window_starts[i] < 0 || cfg->window_starts[i] + n > cfg->full_size)
       return fail("window %d start %d runs past the block", i, cfg->window_starts[i]);
-  if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_MIN) return fail("unknown cumu_mode %d", cfg->cumu_mode);
+  if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_PSD) return fail("unknown cumu_mode %d", cfg->cumu_mode);
   if (mixed && (cfg->hm_width < 0 || (cfg->hm_width && n % cfg->hm_width)))
     return fail("hm_width %d must divide fft_size %d", cfg->hm_width, n);
   if (!mixed && (cfg->hm_width < 0 || (cfg->hm_width && (n % cfg->hm_width || !is_pow2(cfg->hm_width)))))

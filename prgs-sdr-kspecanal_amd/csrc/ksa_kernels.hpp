@@ -16,6 +16,10 @@
 namespace ksa {
 
 enum { CUMU_AVG = 1, CUMU_MAX = 2, CUMU_MIN = 3 };
+// Welch PSD fold (KSA_CUMU_PSD): acc += |X|^2 over the block's windows.  A template constant of the spectrum kernels ONLY: the
+// host passes SpecParams::cumu = CUMU_AVG with it, because the PSD's slot / part combines and its output stage are AVG's (plain
+// sums, times `scale`, no square root) -- so no kernel built before this fold existed sees a new run-time value or a new branch.
+enum { CUMU_PSD = 4 };
 enum { OUT_LINEAR = 0, OUT_DB = 1, OUT_DB_CLIP = 2 };
 enum { FMT_C64 = 0, FMT_U8 = 1 };
 constexpr int HM_ROWS = 128;
@@ -194,7 +198,7 @@ __device__ __forceinline__ void finish_frame(const SpecParams& p, float* red, in
 #ifndef KSA_FINISH_FAST_SMALL
 #define KSA_FINISH_FAST_SMALL 1   // the same for the small transforms (S > 1 slots per workgroup)
 #endif
-  if constexpr (KSA_FINISH_FAST && (S == 1 ? N >= 1024 : KSA_FINISH_FAST_SMALL) && (CM == 0 || CM == CUMU_AVG)) {
+  if constexpr (KSA_FINISH_FAST && (S == 1 ? N >= 1024 : KSA_FINISH_FAST_SMALL) && (CM == 0 || CM == CUMU_AVG || CM == CUMU_PSD)) {
     if (p.cumu == CUMU_AVG && p.out_mode == OUT_LINEAR && g == 0) {      // sdr_curscan's linear spectra; the second stage of N >= 32768
       finish_rows_avg<N, T, S, OUT_LINEAR, 0>(p, red, orow, hm_row, hm_ring, g, tid);
       return;
@@ -233,7 +237,7 @@ __device__ __forceinline__ void finish_frame(const SpecParams& p, float* red, in
 #pragma unroll
         for (int u = 0; u < CH; ++u)
           if (s0 + u < S) x[u] = red4[(s0 + u) * (RS / 4) + q];
-        if (p.cumu == CUMU_AVG) {
+        if (CM == CUMU_PSD || p.cumu == CUMU_AVG) {      // (CM == CUMU_PSD: p.cumu is CUMU_AVG; the constant keeps v_sqrt_f32 out of the PSD kernels)
 #pragma unroll
           for (int u = 0; u < CH; ++u)
             if (s0 + u < S) { r.x += x[u].x; r.y += x[u].y; r.z += x[u].z; r.w += x[u].w; }
@@ -251,7 +255,7 @@ __device__ __forceinline__ void finish_frame(const SpecParams& p, float* red, in
     float o[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      float lin = p.cumu == CUMU_AVG ? o[u] : __builtin_amdgcn_sqrtf(o[u]);
+      float lin = (CM == CUMU_PSD || p.cumu == CUMU_AVG) ? o[u] : __builtin_amdgcn_sqrtf(o[u]);
       lin *= p.scale;
       o[u] = p.out_mode != OUT_LINEAR ? out_db(lin, p.out_mode, p.gain, p.min_amp) : lin;
     }
@@ -628,7 +632,7 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
         if constexpr (S > 1) {
           for (int s2 = 1; s2 < S; ++s2) {
             const float4 x = red4[s2 * (RedStride<N, S>::value / 4) + q];
-            if (p.cumu == CUMU_AVG) { r.x += x.x; r.y += x.y; r.z += x.z; r.w += x.w; }
+            if (CM == CUMU_PSD || p.cumu == CUMU_AVG) { r.x += x.x; r.y += x.y; r.z += x.z; r.w += x.w; }
             else if (p.cumu == CUMU_MAX) { r.x = nan_max(r.x, x.x); r.y = nan_max(r.y, x.y); r.z = nan_max(r.z, x.z); r.w = nan_max(r.w, x.w); }
             else { r.x = nan_min(r.x, x.x); r.y = nan_min(r.y, x.y); r.z = nan_min(r.z, x.z); r.w = nan_min(r.w, x.w); }
           }

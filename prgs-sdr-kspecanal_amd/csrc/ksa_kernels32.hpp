@@ -285,7 +285,13 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
           }
           dft16_tw_at<0>(u, tb[0], tb[1], tb[2], tb[3], tb[4], tb[5]);
         } else dft16_fused_at<0>(u, reinterpret_cast<const float2(&)[15]>(twl[b]));
-        if (cm == CUMU_AVG) {
+        if constexpr (CM == CUMU_PSD) {      // Welch: the sum of |X|^2
+          // (the fence keeps the butterfly and the fold apart in the schedule: without a square root's latency between them
+          //  hipcc interleaves the two and, at N = 16384, spills 12 registers with 20 reloads per window instead of AVG's 4 / 3)
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc[b * 16 + i] = fmaf(u[i].x, u[i].x, fmaf(u[i].y, u[i].y, acc[b * 16 + i]));
+        } else if (cm == CUMU_AVG) {
 #pragma unroll
           for (int i = 0; i < 16; ++i)
             acc[b * 16 + i] = fmaf(wgt, __builtin_amdgcn_sqrtf(fmaf(u[i].x, u[i].x, u[i].y * u[i].y)), acc[b * 16 + i]);

@@ -141,7 +141,10 @@ __global__ __launch_bounds__(64, 4) void spectrum64_kernel(const SpecParams p) {
         dft8<8>(u);
         KSA_STAMP(6);
         const int cm = CM == 0 ? p.cumu : CM;
-        if (cm == CUMU_AVG) {
+        if constexpr (CM == CUMU_PSD) {      // Welch: the sum of |X|^2
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc[i] = fmaf(u[i].x, u[i].x, fmaf(u[i].y, u[i].y, acc[i]));
+        } else if (cm == CUMU_AVG) {
           const int e = k == 0 ? nm1 : nm1 - k + 1;          // closed form of the (a+x)/2 recursion (K:137-139 at K:395)
           const float wgt = ldexpf(1.0f, -e);
 #pragma unroll

@@ -176,7 +176,10 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
       }
       // ---- |X| and the fold over the block's windows (K:391-395), both frames at once ---------------
       const int cm = CM == 0 ? p.cumu : CM;
-      if (cm == CUMU_AVG) {
+      if constexpr (CM == CUMU_PSD) {      // Welch: the sum of |X|^2, two packed FMAs per bin pair
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = fma2(v[i].x, v[i].x, fma2(v[i].y, v[i].y, acc[i]));
+      } else if (cm == CUMU_AVG) {
         const int e = k == 0 ? nm1 : nm1 - k + 1;       // closed form of the (a+x)/2 recursion
         const v2f w = splat(ldexpf(1.0f, -e));
 #pragma unroll

@@ -147,7 +147,11 @@
       // ---- |X| and the fold over this block's windows (K:391-395) ----------------------------
       if (active) {
         const int cm = CM == 0 ? p.cumu : CM;   // CM != 0: the fold mode is a compile-time constant
-        if (cm == CUMU_AVG) {
+        if constexpr (CM == CUMU_PSD) {
+          // Welch: the sum of |X|^2 over the windows, two FMAs per bin -- no square root, no per-window weight
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc[i] = fmaf(v[i].x, v[i].x, fmaf(v[i].y, v[i].y, acc[i]));
+        } else if (cm == CUMU_AVG) {
           // closed form of the (a+x)/2 recursion: weight 2^-(n-k+1), first window 2^-n
           const int e = k == 0 ? nm1 : nm1 - k + 1;
           const float w = ldexpf(1.0f, -e);

@@ -57,6 +57,27 @@ def window_starts(full_size, fft_size, non_overlap):
     return np.asarray(starts, dtype=np.int32)
 
 
+def psd_window_starts(full_size, fft_size, non_overlap):
+    """Segment starts of matplotlib's Welch PSD (mlab.psd behind plt.psd, K:381) for K:375's overlap:
+    noverlap = int(N*(1 - nonOverlap)) -- the reference hands the float product over, which matplotlib >= 3.8 refuses; the
+    truncation is this build's --, step = N - noverlap, K = (fullSize - noverlap) // step segments at k*step.  The hops are
+    constant, unlike K:386's int(k*N*q) (N = 4096, q = 0.1: 410 everywhere against 409 / 410)."""
+    full_size, fft_size = int(full_size), int(fft_size)
+    noverlap = int(fft_size * (1 - non_overlap))
+    step = fft_size - noverlap
+    if not 0 <= noverlap < fft_size or full_size < fft_size:      # (matplotlib: noverlap must be less than NFFT)
+        raise KsaError("no PSD segment fits: fullSize %d fftSize %d nonOverlap %s (0 < nonOverlap <= 1)" % (full_size, fft_size, non_overlap))
+    count = (full_size - noverlap) // step
+    return np.arange(count, dtype=np.int64).astype(np.int32) * np.int32(step)
+
+
+def psd_mag_scale(win, num_segments, fs=2.0):
+    """mlab.psd's scale for a two-sided density (scale_by_freq, mean over the segments), in float64:
+    1 / (Fs * sum(window^2) * K); Fs = 2 is plt.psd's default, which K:381 keeps."""
+    w = np.asarray(win, dtype=np.float64)
+    return 1.0 / (float(fs) * float(np.sum(w * w)) * int(num_segments))
+
+
 def window_table(name, n):
     """K:932-935; accepts the CLI spelling or the 'WIN.X' dict key of the reference."""
     key = name.upper().replace("WIN.", "")
@@ -104,7 +125,7 @@ class SpectrumEngine:
     def __init__(self, fft_size, full_size=None, sampling_rate=2.4e6, non_overlap=0.1, window="ones",
                  cumu_mode="AVG", gain=19.1, min_amp=MIN_AMP_DEFAULT, xres=512, max_frames=1, device=0,
                  scan_total_entries=0, scan_non_overlap=0.5, scan_xres=None,
-                 u8_offset=127.5, u8_scale=127.5, stream=None):
+                 u8_offset=127.5, u8_scale=127.5, stream=None, psd_fs=2.0):
         self.fft_size = int(fft_size)
         if not fft_size_supported(self.fft_size):
             raise KsaError(fft_size_message(self.fft_size))
@@ -122,7 +143,13 @@ class SpectrumEngine:
             raise KsaError("window table has %d taps, fftSize is %d" % (len(win), self.fft_size))
         self.win = win
         self.win_adj = len(win) / np.sum(win)                      # K:373
-        self.starts = window_starts(self.full_size, self.fft_size, self.non_overlap)
+        if self.cumu_mode == "PSD":      # Welch PSD: matplotlib's segments and scale instead of K:386 / K:391
+            self.psd_fs = float(psd_fs)
+            self.starts = psd_window_starts(self.full_size, self.fft_size, self.non_overlap)
+            self.mag_scale = psd_mag_scale(win, len(self.starts), self.psd_fs)
+        else:
+            self.starts = window_starts(self.full_size, self.fft_size, self.non_overlap)
+            self.mag_scale = 2.0 * self.win_adj / self.fft_size    # K:391
         self.hm_width = heatmap_width(self.fft_size, int(xres))
         if self.fft_size % self.hm_width:
             raise KsaError("xRes %d does not divide fftSize %d (the reference fixes xRes up at K:937-949)" % (xres, fft_size))
@@ -142,7 +169,7 @@ class SpectrumEngine:
             num_windows=len(self._starts32),
             window_starts=self._starts32.ctypes.data_as(C.POINTER(C.c_int32)),
             window=self._win32.ctypes.data_as(C.POINTER(C.c_float)),
-            mag_scale=2.0 * self.win_adj / self.fft_size,          # K:391
+            mag_scale=self.mag_scale,
             cumu_mode=CUMU[self.cumu_mode], gain=self.gain, min_amp=self.min_amp, hm_width=self.hm_width,
             max_frames=self.max_frames, u8_offset=u8_offset, u8_scale=u8_scale,
             scan_total_entries=self.scan_total, scan_hop=self.scan_hop, scan_hm_width=self.scan_hm_width)
@@ -192,7 +219,8 @@ class SpectrumEngine:
         return np.ascontiguousarray(a, dtype=np.complex64), FMT_C64
 
     def curscan(self, samples):
-        """One captured block -> float64[fftSize] linear magnitudes, fftshifted (what sdr_curscan returns)."""
+        """One captured block -> float64[fftSize] linear magnitudes, fftshifted (what sdr_curscan returns); with
+        cumu_mode PSD the Welch power density instead (what the reference's sdr_curscan returns under bUsePSD, K:383)."""
         a, fmt = self._host_iq(samples)
         out = np.empty(self.fft_size, dtype=np.float32)
         fn = lib.ksa_curscan_u8 if fmt == FMT_U8 else lib.ksa_curscan_c64

@@ -145,7 +145,7 @@ def handle_args(d, argv=None):
                 break
     if not _engine.fft_size_supported(d["fftSize"]):             # the engine's sizes (the reference takes any, K:391)
         prg_quit(d, "ERROR:handle_args: " + _engine.fft_size_message(d["fftSize"]))
-    if d["curScanCumuMode"] not in ("AVG", "MAX", "MIN", "RAW"):
+    if d["curScanCumuMode"] not in ("AVG", "MAX", "MIN", "RAW", "PSD"):   # PSD: the Welch fold on the device (additive)
         prg_quit(d, "ERROR: Unknown cumuMode [{}], Quiting...".format(d["curScanCumuMode"]))
     if d["frameBatch"] < 1:
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] must be >= 1".format(d["frameBatch"]))
@@ -265,18 +265,23 @@ def get_engine(d, scan_total=0, max_frames=1):
 def psd_crosscheck(d, samples, mag):
     """bUsePSD (K:350, K:374-384, README.rst:523-529) as a CPU-only DIAGNOSTIC next to the GPU result, never in
     place of it: matplotlib's Welch PSD of the same block (mlab.psd, the routine behind plt.psd at K:382: Fs = 2,
-    two-sided, scale_by_freq, mean over segments) is converted back to this program's amplitude convention
-    (|X| = sqrt(P * Fs * sum(w^2)), then 2*winAdj/N as K:391) and compared at the strongest bin.  The reference's own
-    branch passes a float `noverlap` and raises TypeError under matplotlib >= 3.8 (observed with 3.10 in the build
-    container), so there is no reference-run vector for it: parity unpinned, diagnostic only.  Stores d['psd.cur']
-    (the PSD, fftshifted) and d['psd.check'] = (bin_gpu, bin_psd, level_gpu_dB, level_psd_dB)."""
+    two-sided, scale_by_freq, mean over segments) is compared with the device result at the strongest bin.  Under the
+    magnitude folds (AVG / MAX / MIN / RAW) it is first converted back to this program's amplitude convention
+    (|X| = sqrt(P * Fs * sum(w^2)), then 2*winAdj/N as K:391); under curScanCumuMode PSD the device folded the same Welch
+    PSD, so `pxx` itself is compared with it.  `noverlap` is truncated to an int: the reference's own branch passes the
+    float and raises TypeError under matplotlib >= 3.8 (tests/golden/psd_*.npz are runs of the reference with that one
+    shim).  Stores d['psd.cur'] (the linear PSD, fftshifted) and d['psd.check'] = (bin_gpu, bin_psd, level_gpu_dB,
+    level_psd_dB)."""
     from matplotlib import mlab
     n, win = d["fftSize"], np.asarray(d["theWin"], dtype=np.float64)
     x = np.asarray(samples)
     if x.dtype == np.uint8:
         x = (x[0::2].astype(np.float64) - 127.5) / 127.5 + 1j * ((x[1::2].astype(np.float64) - 127.5) / 127.5)
     pxx, _ = mlab.psd(x.astype(np.complex128), NFFT=n, window=win, noverlap=int(n * (1 - d["curScanNonOverlap"])))
-    amp = np.sqrt(pxx * 2.0 * np.sum(win ** 2)) * 2.0 * (n / np.sum(win)) / n
+    if d["curScanCumuMode"] == "PSD":      # the device folded the same Welch PSD: like is compared with like
+        amp = pxx
+    else:
+        amp = np.sqrt(pxx * 2.0 * np.sum(win ** 2)) * 2.0 * (n / np.sum(win)) / n
     kg, kp = int(np.argmax(mag)), int(np.argmax(amp))
     with np.errstate(divide="ignore"):
         lg, lp = 10 * np.log10(mag[kg]) - d["gain"], 10 * np.log10(amp[kp]) - d["gain"]
@@ -285,7 +290,8 @@ def psd_crosscheck(d, samples, mag):
 
 
 def sdr_curscan(d):
-    """Drop-in for K:351-397: float64[fftSize] linear magnitudes, fftshifted."""
+    """Drop-in for K:351-397: float64[fftSize], fftshifted -- linear magnitudes, or under curScanCumuMode PSD the linear
+    Welch PSD (what K:383 returns under bUsePSD)."""
     samples = sdr_read(d["sdr"], d["fullSize"], raw=d.get("iqFormat") == "u8")
     mag = get_engine(d).curscan(samples)
     if d["bUsePSD"]:
