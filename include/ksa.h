@@ -47,6 +47,15 @@ enum { KSA_CUMU_PSD = 4 };
 /* IQ sample formats: complex64 (what sdr.read_samples hands over, narrowed from K:335's complex128)
  * and the dongle's native interleaved uint8 I,Q (pyrtlsdr packed_bytes_to_iq; K:301, K:339, K:346) */
 enum { KSA_FMT_C64 = 0, KSA_FMT_U8 = 1 };
+/* Fixed-point capture formats: interleaved I,Q, little-endian, signed, fixed scaling, no offset (u8_offset / u8_scale do not
+ * apply).  KSA_FMT_S8: int8 pairs, sample = b / 128 (HackRF, SigMF ci8), 2 bytes per sample, IQ pointer 2-byte aligned.
+ * KSA_FMT_S16: int16 pairs, sample = b / 32768 (USRP sc16, SigMF ci16_le, Airspy, SDRplay), 4 bytes per sample, IQ pointer
+ * 4-byte aligned.  frame_stride stays in samples.  Every entry point that takes `fmt` accepts them, and since the scale is a
+ * power of two the result is the one of the complex64 form of the same values, (float)b / 128 or / 32768.  Host-pointer entry
+ * points are named by format and none exists for these two: see the note on ksa_host_alloc for the way in from host memory.
+ * The layout and the calls are unchanged, so the ABI number is too: a library without these formats refuses them
+ * ("unknown sample format 2"). */
+enum { KSA_FMT_S8 = 2, KSA_FMT_S16 = 3 };
 /* what the spectrum kernel writes per frame */
 enum {
   KSA_OUT_LINEAR = 0,  /* sdr_curscan's return value: linear magnitude, fftshifted (K:391-396) */
@@ -263,6 +272,11 @@ int ksa_read_view(ksa_engine* e, int32_t scan, int32_t mode, int32_t cells, floa
                   int32_t hm_rows, float* hm_rows_host, int32_t* hm_index);
 
 /* ---- pinned host memory for capture blocks (optional: any host pointer works, pinned ones copy faster) ------------ */
+/* Memory from ksa_host_alloc is page-locked AND mapped into the device's address space (hipHostMalloc): it may also be handed
+ * as the IQ pointer of the `_dev` entry points (curscan, frames, scan pass / passes / spectra), in any sample format.  The
+ * kernels then read it over the host link, once per window that covers a sample (the overlap is not cached on the device side
+ * of the link), and the call is asynchronous like every `_dev` call: synchronise before the memory is reused.  This is the
+ * route for KSA_FMT_S8 / KSA_FMT_S16 blocks that live in host memory. */
 int ksa_host_alloc(void** out, int64_t bytes);
 int ksa_host_free(void* p);
 

@@ -12,6 +12,7 @@ ABI_VERSION = 5
 HM_ROWS = 128
 CUMU = {"RAW": 0, "AVG": 1, "MAX": 2, "MIN": 3, "PSD": 4}
 FMT_C64, FMT_U8 = 0, 1
+FMT_S8, FMT_S16 = 2, 3      # interleaved signed int8 (b / 128) and little-endian int16 (b / 32768) I,Q
 OUT_LINEAR, OUT_DB, OUT_DB_CLIP = 0, 1, 2
 
 

@@ -196,6 +196,7 @@ int plan_of(const ksa_engine* e, const SpecParams& p) { return std::max(p.nframe
 // KSA_CUMU_PSD engines run the CUMU_PSD instantiation of every spectrum kernel (a template constant everywhere, also where the
 // other folds branch at run time) with SpecParams::cumu = CUMU_AVG: the combines and the output stage of the two are the same.
 bool fold_psd(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PSD; }
+size_t sample_bytes(int fmt);   // bytes per IQ sample of a KSA_FMT_* value
 
 template <int N, int FMT, int RM, int CM>
 int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only);
@@ -449,7 +450,9 @@ int launch_mr(ksa_engine* e, const SpecParams& p, bool configure_only) {
   if constexpr (!PSD) {
     if (fold_psd(e)) return launch_mr<FMT, true>(e, p, configure_only);
   }
-  auto kfn = PSD ? ksa::mixed_radix_psd_kernel<FMT> : ksa::mixed_radix_kernel<FMT>;
+  void (*kfn)(const SpecParams, const ksa::MrPlan);
+  if constexpr (FMT == ksa::FMT_S8 || FMT == ksa::FMT_S16) kfn = ksa::mixed_radix_fixed_kernel<FMT, PSD ? ksa::CUMU_PSD : 0>;
+  else kfn = PSD ? ksa::mixed_radix_psd_kernel<FMT> : ksa::mixed_radix_kernel<FMT>;
   const int lds_bytes = e->mr.n * (int)sizeof(float2);
   if (configure_only) {
     // (one kernel serves every N of the path: its attribute is set to the largest transform, not to this engine's)
@@ -556,12 +559,18 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int 
     if (R == 16) {
       const dim3 ga(n1 / 512, nwin, cf);     // two adjacent n1 per thread
       if (fmt == KSA_FMT_C64) hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_C64>, ga, dim3(256), 0, e->stream, a);
+      else if (fmt == KSA_FMT_S8) hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_S8>, ga, dim3(256), 0, e->stream, a);
+      else if (fmt == KSA_FMT_S16) hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_S16>, ga, dim3(256), 0, e->stream, a);
       else hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_U8>, ga, dim3(256), 0, e->stream, a);
     } else {
       const dim3 ga(n1 / 256, nwin, cf);     // one n1 per thread, 32 or 64 samples in registers
       if (R == 32 && fmt == KSA_FMT_C64) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_C64, 32>), ga, dim3(256), 0, e->stream, a);
+      else if (R == 32 && fmt == KSA_FMT_S8) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S8, 32>), ga, dim3(256), 0, e->stream, a);
+      else if (R == 32 && fmt == KSA_FMT_S16) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S16, 32>), ga, dim3(256), 0, e->stream, a);
       else if (R == 32) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_U8, 32>), ga, dim3(256), 0, e->stream, a);
       else if (fmt == KSA_FMT_C64) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_C64, 64>), ga, dim3(256), 0, e->stream, a);
+      else if (fmt == KSA_FMT_S8) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S8, 64>), ga, dim3(256), 0, e->stream, a);
+      else if (fmt == KSA_FMT_S16) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S16, 64>), ga, dim3(256), 0, e->stream, a);
       else hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_U8, 64>), ga, dim3(256), 0, e->stream, a);
     }
     SpecParams b{};
@@ -613,14 +622,14 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int 
 int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, int out_mode,
                  float* out, bool with_hm, float* hm_rows, int batch_first = 0, int batch_frames = 0) {
   const ksa_config& c = e->cfg;
-  if (fmt != KSA_FMT_C64 && fmt != KSA_FMT_U8) return fail("unknown sample format %d", fmt);
+  if (fmt != KSA_FMT_C64 && fmt != KSA_FMT_U8 && fmt != KSA_FMT_S8 && fmt != KSA_FMT_S16) return fail("unknown sample format %d", fmt);
   if (nframes < 1 || nframes > c.max_frames) return fail("nframes %d outside 1..max_frames(%d)", nframes, c.max_frames);
   if (stride < 0) return fail("negative frame_stride");
   if (stride > (1ll << 27)) return fail("frame_stride %lld exceeds 2^27 samples", stride);
   // the output stage stores float4 runs; IQ loads are per-sample but frames should start on sample bounds
   if ((reinterpret_cast<uintptr_t>(out) & 15) || (hm_rows && (reinterpret_cast<uintptr_t>(hm_rows) & 15)))
     return fail("device output buffers must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(iq) & (fmt == KSA_FMT_C64 ? 7 : 1)) return fail("IQ buffer is not sample aligned");
+  if (reinterpret_cast<uintptr_t>(iq) & (sample_bytes(fmt) - 1)) return fail("IQ buffer is not sample aligned");
   SpecParams p{};
   p.iq = iq;
   p.frame_stride = stride;
@@ -668,9 +677,11 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   if (e->path == 2) {
     rc = run_dif16(e, p, fmt, batch_first, batch_frames);
   } else if (e->path == 6) {
-    rc = fmt == KSA_FMT_C64 ? launch_mr<ksa::FMT_C64>(e, p, false) : launch_mr<ksa::FMT_U8>(e, p, false);
+    rc = fmt == KSA_FMT_C64 ? launch_mr<ksa::FMT_C64>(e, p, false) : fmt == KSA_FMT_S8 ? launch_mr<ksa::FMT_S8>(e, p, false)
+         : fmt == KSA_FMT_S16 ? launch_mr<ksa::FMT_S16>(e, p, false) : launch_mr<ksa::FMT_U8>(e, p, false);
   } else {
-    rc = fmt == KSA_FMT_C64 ? launch_spec_n<ksa::FMT_C64>(e, p, false) : launch_spec_n<ksa::FMT_U8>(e, p, false);
+    rc = fmt == KSA_FMT_C64 ? launch_spec_n<ksa::FMT_C64>(e, p, false) : fmt == KSA_FMT_S8 ? launch_spec_n<ksa::FMT_S8>(e, p, false)
+         : fmt == KSA_FMT_S16 ? launch_spec_n<ksa::FMT_S16>(e, p, false) : launch_spec_n<ksa::FMT_U8>(e, p, false);
   }
   e->plan_frames = 0;
   if (rc) return rc;
@@ -772,7 +783,7 @@ int scan_reset(ksa_engine* e) {
   return 0;
 }
 
-size_t sample_bytes(int fmt) { return fmt == KSA_FMT_C64 ? 8 : 2; }
+size_t sample_bytes(int fmt) { return fmt == KSA_FMT_C64 ? 8 : fmt == KSA_FMT_S16 ? 4 : 2; }
 
 // Grow-only device scratch of an engine (on its device, which the caller has made current).
 template <typename T>
@@ -850,6 +861,8 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
     SpecParams dummy{};
     if ((rc = launch_mr<ksa::FMT_C64>(e, dummy, true))) return bail(rc);
     if ((rc = launch_mr<ksa::FMT_U8>(e, dummy, true))) return bail(rc);
+    if ((rc = launch_mr<ksa::FMT_S8>(e, dummy, true))) return bail(rc);
+    if ((rc = launch_mr<ksa::FMT_S16>(e, dummy, true))) return bail(rc);
   } else {
     e->path = n <= 16384 ? 0 : 2;
     e->dif_radix = n <= 262144 ? 16 : n == 524288 ? 32 : 64;
@@ -957,6 +970,8 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
     dummy.nwin = cfg->num_windows;
     if ((rc = launch_spec_n<ksa::FMT_C64>(e, dummy, true))) return bail(rc);
     if ((rc = launch_spec_n<ksa::FMT_U8>(e, dummy, true))) return bail(rc);
+    if ((rc = launch_spec_n<ksa::FMT_S8>(e, dummy, true))) return bail(rc);
+    if ((rc = launch_spec_n<ksa::FMT_S16>(e, dummy, true))) return bail(rc);
     if (e->path == 2) {
       const int n1 = sn, nw = cfg->num_windows;
       // first-stage output twiddles W_N^(n1*e), e = 1,2,3,4,8,12 (float64-generated); w^k2 = w^(k2&3) * w^(k2&12)

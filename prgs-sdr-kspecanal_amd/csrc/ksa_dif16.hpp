@@ -25,7 +25,7 @@
 namespace ksa {
 
 struct DifParams {
-  const void* iq;            // float2[] or uchar2[]; frame f at sample f*frame_stride
+  const void* iq;            // float2[], uchar2[], char2[] or short2[]; frame f at sample f*frame_stride
   long long frame_stride;
   int frame0;                // first frame of this chunk
   int nwin;
@@ -59,6 +59,31 @@ __global__ __launch_bounds__(256) void dif16_kernel(const DifParams p) {
       } else {
         xa = src[0]; xb = src[1];
       }
+    } else if constexpr (FMT == FMT_S16) {
+      // no taps to fold the scale into here (the window multiply below is shared with complex64): b * 2^-15 is exact
+      const short2* src = reinterpret_cast<const short2*>(p.iq) + base + (long long)N1 * q;
+      short4 b;
+      if ((reinterpret_cast<uintptr_t>(src) & 7) == 0) {
+        b = *reinterpret_cast<const short4*>(src);
+      } else {
+        const short2 b0 = src[0], b1 = src[1];
+        b = make_short4(b0.x, b0.y, b1.x, b1.y);
+      }
+      constexpr float sc = fmt_fixed_scale(FMT_S16);
+      xa = make_float2((float)b.x * sc, (float)b.y * sc);
+      xb = make_float2((float)b.z * sc, (float)b.w * sc);
+    } else if constexpr (FMT == FMT_S8) {
+      const char2* src = reinterpret_cast<const char2*>(p.iq) + base + (long long)N1 * q;
+      char4 b;
+      if ((reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+        b = *reinterpret_cast<const char4*>(src);
+      } else {
+        const char2 b0 = src[0], b1 = src[1];
+        b = make_char4(b0.x, b0.y, b1.x, b1.y);
+      }
+      constexpr float sc = fmt_fixed_scale(FMT_S8);
+      xa = make_float2((float)b.x * sc, (float)b.y * sc);
+      xb = make_float2((float)b.z * sc, (float)b.w * sc);
     } else {
       const uchar2* src = reinterpret_cast<const uchar2*>(p.iq) + base + (long long)N1 * q;
       uchar4 b;
@@ -157,6 +182,12 @@ __global__ __launch_bounds__(256) void dif_wide_kernel(const DifParams p) {
     float2 x;
     if constexpr (FMT == FMT_C64) {
       x = (reinterpret_cast<const float2*>(p.iq) + base)[(long long)N1 * q];
+    } else if constexpr (FMT == FMT_S16) {
+      const short2 b = (reinterpret_cast<const short2*>(p.iq) + base)[(long long)N1 * q];
+      x = make_float2((float)b.x * fmt_fixed_scale(FMT_S16), (float)b.y * fmt_fixed_scale(FMT_S16));
+    } else if constexpr (FMT == FMT_S8) {
+      const char2 b = (reinterpret_cast<const char2*>(p.iq) + base)[(long long)N1 * q];
+      x = make_float2((float)b.x * fmt_fixed_scale(FMT_S8), (float)b.y * fmt_fixed_scale(FMT_S8));
     } else {
       const uchar2 b = (reinterpret_cast<const uchar2*>(p.iq) + base)[(long long)N1 * q];
       x = make_float2(((float)b.x - p.u8_offset) * p.u8_inv_scale, ((float)b.y - p.u8_offset) * p.u8_inv_scale);

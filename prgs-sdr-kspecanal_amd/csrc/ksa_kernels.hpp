@@ -21,11 +21,11 @@ enum { CUMU_AVG = 1, CUMU_MAX = 2, CUMU_MIN = 3 };
 // sums, times `scale`, no square root) -- so no kernel built before this fold existed sees a new run-time value or a new branch.
 enum { CUMU_PSD = 4 };
 enum { OUT_LINEAR = 0, OUT_DB = 1, OUT_DB_CLIP = 2 };
-enum { FMT_C64 = 0, FMT_U8 = 1 };
+enum { FMT_C64 = 0, FMT_U8 = 1, FMT_S8 = 2, FMT_S16 = 3 };
 constexpr int HM_ROWS = 128;
 
 struct SpecParams {
-  const void* iq;           // float2[] or uchar2[]; frame f starts at sample f*frame_stride
+  const void* iq;           // float2[], uchar2[], char2[] or short2[]; frame f starts at sample f*frame_stride
   long long frame_stride;
   int frame_len;            // samples readable from a frame's start (range-checked by the buffer loads)
   int nframes;
@@ -312,6 +312,27 @@ __device__ __forceinline__ void finish_frame(const SpecParams& p, float* red, in
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
+// ---- sample formats of the load stages ---------------------------------------------------------------------------------------
+// complex64 (8 bytes), offset-binary uint8 (2 bytes, (b - u8_offset) / u8_scale), and the fixed-point capture formats: signed
+// int8 (2 bytes, b / 128) and signed int16 (4 bytes, little-endian, b / 32768).  A sample is ONE load in every format; its raw
+// bits wait in registers of RawOf<FMT>::type until the window multiply.  The scale of the narrow formats is folded into the taps
+// (tap_scale), which for the two signed formats is a power of two: exact, so their output equals complex64's of the same values.
+__host__ __device__ constexpr int fmt_bytes(int fmt) { return fmt == FMT_C64 ? 8 : fmt == FMT_S16 ? 4 : 2; }
+__host__ __device__ constexpr float fmt_fixed_scale(int fmt) { return fmt == FMT_S8 ? 0x1p-7f : fmt == FMT_S16 ? 0x1p-15f : 1.0f; }
+template <int FMT> struct RawOf { typedef unsigned short type; };
+template <> struct RawOf<FMT_C64> { typedef u32x2 type; };
+template <> struct RawOf<FMT_S16> { typedef unsigned int type; };
+template <> struct RawOf<FMT_S8> { typedef unsigned int type; };    // (held in 16 bits hipcc shifts every Q byte up before it converts it)
+template <int FMT>
+__device__ __forceinline__ float tap_scale(const SpecParams& p) { return FMT == FMT_U8 ? p.u8_inv_scale : fmt_fixed_scale(FMT); }
+// I, Q of one int8 / int16 sample as floats, unscaled: sign-extend the two halves of the load and convert
+template <int FMT>
+__device__ __forceinline__ float2 unpack_signed(unsigned b) {
+  static_assert(FMT == FMT_S8 || FMT == FMT_S16, "signed fixed-point formats only");
+  if constexpr (FMT == FMT_S8) return make_float2((float)(int)(signed char)(b & 0xff), (float)(int)(signed char)((b >> 8) & 0xff));
+  else return make_float2((float)(int)(short)(b & 0xffff), (float)((int)b >> 16));
+}
+
 // In-kernel cycle stamps (diagnostic build only; never compiled into the shipped library).
 #ifdef KSA_STAMPS
 #define KSA_STAMP(i)                                                                        \
@@ -453,7 +474,7 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
   static_assert(RM == 0 || Plan<N>::S == 1, "sample reuse needs one transform per workgroup");
   using P = Plan<N>;
   constexpr int L = P::L, T = P::T, S = P::S, M = P::M, R0 = P::R0, B0 = P::B0, NPAD = P::NPAD;
-  constexpr int SB = FMT == FMT_C64 ? 8 : 2;  // bytes per IQ sample
+  constexpr int SB = fmt_bytes(FMT);  // bytes per IQ sample
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
   float2* const tw_lds = lds + S * NPAD;
 
@@ -469,11 +490,11 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
   if constexpr (WIN_LDS) {
     for (int i = tid; i < N; i += T) {       // tap of sample n = l' + L*q lives at ((q>>2)*L + l')*4 + (q&3)
       const int q = i / L, ll = i - q * L;
-      win_lds[((q >> 2) * L + ll) * 4 + (q & 3)] = p.window[i] * (FMT == FMT_U8 ? p.u8_inv_scale : 1.0f);
+      win_lds[((q >> 2) * L + ll) * 4 + (q & 3)] = p.window[i] * tap_scale<FMT>(p);
     }
   } else if constexpr (!Tune<N>::WIN_GLOBAL) {
 #pragma unroll
-    for (int q = 0; q < 16; ++q) win[q] = p.window[l + L * q] * (FMT == FMT_U8 ? p.u8_inv_scale : 1.0f);
+    for (int q = 0; q < 16; ++q) win[q] = p.window[l + L * q] * tap_scale<FMT>(p);
   }
   // last pass: k = l.  FUSED: the 15 folded twiddles of dft16_fused (rows of the [15][N/16] table);
   // otherwise rows t = 1,2,3,4,8,12 of the plain w^t table for dft16_tw.
@@ -515,7 +536,7 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
   // every load in a readfirstlane "waterfall" loop) and spans exactly this frame: every load is range-checked
   // by the hardware.  Prefetching the next window into a second register set was measured and dropped
   // (spills: 104 -> 165 M FFT/s without it at the 0.1 hop; 2.5 -> 1.6 ms with sample reuse).
-  typedef typename std::conditional<FMT == FMT_C64, u32x2, unsigned short>::type raw_t;
+  typedef typename RawOf<FMT>::type raw_t;
   raw_t raw[16];
   const int start0 = p.starts[0];
   auto issue_loads = [&](int fr, int k, int q0, auto rotc) {
@@ -536,6 +557,7 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
 #define KSA_LOAD_AUX 0   // cache policy of the IQ loads (experiments: 2 = nt)
 #endif
       if constexpr (FMT == FMT_C64) raw[(q + ROT) & 15] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, L * q * SB, KSA_LOAD_AUX);
+      else if constexpr (FMT == FMT_S16) raw[(q + ROT) & 15] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, L * q * SB, 0);
       else raw[(q + ROT) & 15] = __builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, L * q * SB, 0);
 #endif
     }

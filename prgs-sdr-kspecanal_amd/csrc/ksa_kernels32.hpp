@@ -83,7 +83,7 @@ template <int N, int FMT, int CM>
 __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kernel(const SpecParams p) {
   using P = Plan32<N>;
   constexpr int L = P::L, T = P::T, R1 = P::R1, B1 = P::B1;
-  constexpr int SB = FMT == FMT_C64 ? 8 : 2;
+  constexpr int SB = fmt_bytes(FMT);
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
   float2* const my = lds;
   float2* const tw_lds = lds + P::NPAD;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
   const int nm1 = p.nwin - 1;
   const int NP = p.parts > 1 ? p.parts : 1;
   const int total = p.nframes * NP;
-  typedef typename std::conditional<FMT == FMT_C64, u32x2, unsigned short>::type raw_t;
+  typedef typename RawOf<FMT>::type raw_t;
   const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.window), 0, N * 4, 0x00020000);
   const auto twrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(p.tw_last), 0, 30 * L * 8, 0x00020000);
   // Taps of the thread's 32 samples l + L*q.  The host hands this kernel the window table re-ordered as [8][L][4]
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
 #if !KSA32_TAPS_X4
 #pragma unroll
     for (int q = 0; q < 32; ++q)
-      win[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, l * 4, L * q * 4, 0)) * (FMT == FMT_U8 ? p.u8_inv_scale : 1.0f);
+      win[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, l * 4, L * q * 4, 0)) * tap_scale<FMT>(p);
     return;
 #endif
 #pragma unroll
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
       for (int j = 0; j < 4; ++j) win[4 * q4 + j] = (float)(l + 4 * q4 + j) * p.u8_inv_scale;
 #else
       const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, l * 16, q4 * L * 16, 0);
-      const float sc = FMT == FMT_U8 ? p.u8_inv_scale : 1.0f;
+      const float sc = tap_scale<FMT>(p);
       win[4 * q4 + 0] = __uint_as_float(w.x) * sc;
       win[4 * q4 + 1] = __uint_as_float(w.y) * sc;
       win[4 * q4 + 2] = __uint_as_float(w.z) * sc;
@@ -159,6 +159,7 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
       else raw[q] = voff + q;
 #else
       if constexpr (FMT == FMT_C64) raw[q] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, L * q * SB, 0);
+      else if constexpr (FMT == FMT_S16) raw[q] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, L * q * SB, 0);
       else raw[q] = __builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, L * q * SB, 0);
 #endif
     }
@@ -205,6 +206,9 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
         if constexpr (FMT == FMT_C64) {
           const unsigned xr = raw[q].x, xi = raw[q].y;
           v[q] = make_float2(__uint_as_float(xr) * win[q], __uint_as_float(xi) * win[q]);
+        } else if constexpr (FMT == FMT_S8 || FMT == FMT_S16) {
+          const float2 x = unpack_signed<FMT>(raw[q]);
+          v[q] = make_float2(x.x * win[q], x.y * win[q]);
         } else {
           const unsigned short x = raw[q];
           v[q] = make_float2(((float)(x & 0xff) - p.u8_offset) * win[q], ((float)(x >> 8) - p.u8_offset) * win[q]);

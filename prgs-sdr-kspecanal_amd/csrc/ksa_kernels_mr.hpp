@@ -84,9 +84,9 @@ template <int FMT, int R>
 __device__ __forceinline__ void mr_first(const SpecParams& p, const char* fbase, int start, float2* lds, int n, int tid, int T) {
   constexpr int NB = MrNb<R>::value;
   mr_opaque(tid, n);
-  constexpr int SB = FMT == FMT_C64 ? 8 : 2;
+  constexpr int SB = fmt_bytes(FMT);
   const int m = n / R;
-  const float tap_scale = FMT == FMT_U8 ? p.u8_inv_scale : 1.0f;
+  const float tap_sc = tap_scale<FMT>(p);
   const auto irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(fbase), 0, p.frame_len * SB, 0x00020000);
   const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.window), 0, n * 4, 0x00020000);
   float2 v[NB][R];
@@ -96,12 +96,16 @@ __device__ __forceinline__ void mr_first(const SpecParams& p, const char* fbase,
     if (j < m) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const float w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, j * 4, r * m * 4, 0)) * tap_scale;
+        const float w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, j * 4, r * m * 4, 0)) * tap_sc;
         float2 x;
         if constexpr (FMT == FMT_C64) {
           const u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(irsrc, (start + j) * SB, r * m * SB, 0);
           const unsigned xr = b.x, xi = b.y;
           x = make_float2(__uint_as_float(xr), __uint_as_float(xi));
+        } else if constexpr (FMT == FMT_S16) {
+          x = unpack_signed<FMT>(__builtin_amdgcn_raw_buffer_load_b32(irsrc, (start + j) * SB, r * m * SB, 0));
+        } else if constexpr (FMT == FMT_S8) {
+          x = unpack_signed<FMT>(__builtin_amdgcn_raw_buffer_load_b16(irsrc, (start + j) * SB, r * m * SB, 0));
         } else {
           const unsigned short b = __builtin_amdgcn_raw_buffer_load_b16(irsrc, (start + j) * SB, r * m * SB, 0);
           x = make_float2((float)(b & 0xff) - p.u8_offset, (float)(b >> 8) - p.u8_offset);
@@ -194,6 +198,15 @@ __global__ __launch_bounds__(MR_MAX_THREADS) void mixed_radix_kernel(const SpecP
 template <int FMT>
 __global__ __launch_bounds__(MR_MAX_THREADS) void mixed_radix_psd_kernel(const SpecParams p, const MrPlan plan) {
   constexpr int CM = CUMU_PSD;
+#include "ksa_mr_body.inc"
+}
+
+// The int8 / int16 forms (FMT_S8, FMT_S16) of both, again under a name of their own: mixed_radix_kernel / mixed_radix_psd_kernel stay
+// one kernel per format of the complex64 / uint8 pair.  CMX = 0 (the run-time fold) or CUMU_PSD.
+template <int FMT, int CMX>
+__global__ __launch_bounds__(MR_MAX_THREADS) void mixed_radix_fixed_kernel(const SpecParams p, const MrPlan plan) {
+  static_assert(FMT == FMT_S8 || FMT == FMT_S16, "signed fixed-point formats only");
+  constexpr int CM = CMX;
 #include "ksa_mr_body.inc"
 }
 

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
   using P = Plan<N>;
   using PP = PlanPair<N>;
   constexpr int L = P::L, T = P::T, M = P::M, R0 = P::R0, B0 = P::B0, NPAD = PP::NPAD;
-  constexpr int SB = FMT == FMT_C64 ? 8 : 2;
+  constexpr int SB = fmt_bytes(FMT);
   extern __shared__ __attribute__((aligned(16))) cx2 lds2[];
   cx2* const my = lds2;
   float2* const tw_lds = reinterpret_cast<float2*>(lds2 + NPAD);
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
 
   float win[16];
 #pragma unroll
-  for (int q = 0; q < 16; ++q) win[q] = p.window[l + L * q] * (FMT == FMT_U8 ? p.u8_inv_scale : 1.0f);
+  for (int q = 0; q < 16; ++q) win[q] = p.window[l + L * q] * tap_scale<FMT>(p);
 #ifndef KSAP_TW6
 #define KSAP_TW6 1   // last pass from 6 twiddles (12 VGPRs) instead of the 15 folded ones (30 VGPRs)
 #endif
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
   }
 
   const int nm1 = p.nwin - 1;
-  typedef typename std::conditional<FMT == FMT_C64, u32x2, unsigned short>::type raw_t;
+  typedef typename RawOf<FMT>::type raw_t;
   raw_t ra[16], rb[16];
   const int start0 = p.starts[0];
   // 16 samples l + L*q of one window of both frames (8 B/lane, wave-uniform descriptors, range-checked); with sample
@@ -84,6 +84,9 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
       if constexpr (FMT == FMT_C64) {
         ra[q] = __builtin_amdgcn_raw_buffer_load_b64(rsa, voff, L * q * SB, 0);
         rb[q] = __builtin_amdgcn_raw_buffer_load_b64(rsb, voff, L * q * SB, 0);
+      } else if constexpr (FMT == FMT_S16) {
+        ra[q] = __builtin_amdgcn_raw_buffer_load_b32(rsa, voff, L * q * SB, 0);
+        rb[q] = __builtin_amdgcn_raw_buffer_load_b32(rsb, voff, L * q * SB, 0);
       } else {
         ra[q] = __builtin_amdgcn_raw_buffer_load_b16(rsa, voff, L * q * SB, 0);
         rb[q] = __builtin_amdgcn_raw_buffer_load_b16(rsb, voff, L * q * SB, 0);
@@ -111,6 +114,10 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
           const unsigned ar = ra[q].x, ai = ra[q].y, br = rb[q].x, bi = rb[q].y;
           e.x.x = __uint_as_float(ar) * win[q]; e.x.y = __uint_as_float(br) * win[q];
           e.y.x = __uint_as_float(ai) * win[q]; e.y.y = __uint_as_float(bi) * win[q];
+        } else if constexpr (FMT == FMT_S8 || FMT == FMT_S16) {
+          const float2 xa = unpack_signed<FMT>(ra[q]), xb = unpack_signed<FMT>(rb[q]);
+          e.x.x = xa.x * win[q]; e.x.y = xb.x * win[q];
+          e.y.x = xa.y * win[q]; e.y.y = xb.y * win[q];
         } else {
           const unsigned short xa = ra[q], xb = rb[q];
           e.x.x = ((float)(xa & 0xff) - p.u8_offset) * win[q]; e.x.y = ((float)(xb & 0xff) - p.u8_offset) * win[q];

@@ -2,7 +2,7 @@
 // ksa_window_body.inc is included by spectrum_kernel).  Expects in scope: FMT, p, plan and CM -- CUMU_PSD, or 0 = the
 // AVG / MAX / MIN fold decided at run time from p.cumu.
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
-  constexpr int SB = FMT == FMT_C64 ? 8 : 2;   // bytes per IQ sample
+  constexpr int SB = fmt_bytes(FMT);   // bytes per IQ sample
   constexpr int NBL = MrNb<4>::value;          // butterflies per thread of the last (radix-4) pass
   const int T = blockDim.x;
   const int nm1 = p.nwin - 1;

@@ -13,7 +13,7 @@
           const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.window), 0, N * 4, 0x00020000);
 #pragma unroll
           for (int q = 0; q < 16; ++q)
-            win[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, l * 4, L * q * 4, 0)) * (FMT == FMT_U8 ? p.u8_inv_scale : 1.0f);
+            win[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, l * 4, L * q * 4, 0)) * tap_scale<FMT>(p);
         }
         if constexpr (WIN_LDS) {
 #pragma unroll
@@ -30,6 +30,8 @@
             // (scalar copies first: __builtin_bit_cast on a vector element reads element 0 twice)
             const unsigned xr = raw[(q + 8 * PAR) & 15].x, xi = raw[(q + 8 * PAR) & 15].y;
             x = make_float2(__uint_as_float(xr), __uint_as_float(xi));
+          } else if constexpr (FMT == FMT_S8 || FMT == FMT_S16) {
+            x = unpack_signed<FMT>(raw[(q + 8 * PAR) & 15]);   // b * w, taps pre-multiplied by 2^-7 / 2^-15
           } else {
             const unsigned short b = raw[(q + 8 * PAR) & 15];   // (b - offset)/scale * w, taps pre-divided by the scale
             x = make_float2((float)(b & 0xff) - p.u8_offset, (float)(b >> 8) - p.u8_offset);
@@ -37,6 +39,10 @@
           if constexpr (Tune<N>::WIN_FUSED) { v[pos] = x; wpos[pos] = win[q]; }
           else v[pos] = make_float2(x.x * win[q], x.y * win[q]);
         }
+        // int8 / int16, rolled sample-reuse loop: a scheduling fence behind the unpack.  Without it hipcc spreads the 32 conversions
+        // over the first pass, and spectrum_kernel<1024, int16, RM = 4, MIN> ends at the 168-VGPR cap with 5 spilled registers (161
+        // and none with it).  Not on the general path: there the fence costs the N = 16 kernels a wave per SIMD (82 VGPRs).
+        if constexpr ((FMT == FMT_S8 || FMT == FMT_S16) && RM > 0 && !PP) __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (PP) {
         // ping-pong: the window's old half is dead, its registers take the next window's new half, and the halves swap roles

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import lib, check, Config, CUMU, FMT_C64, FMT_U8, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS, KsaError
+from ._lib import lib, check, Config, CUMU, FMT_C64, FMT_U8, FMT_S8, FMT_S16, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS, KsaError
 
 MIN_AMP_DEFAULT = (1 / 256) * 0.00001   # gMinAmp4Clip K:53
 FFT2FULL_LESS, FFT2FULL_MORE = 8, 2     # K:49-50
@@ -110,6 +110,24 @@ def _ptr(a):
     return a
 
 
+_PINNED = {}     # address -> bytes of every live PinnedBuffer
+
+
+def _is_pinned(a):
+    """True when the numpy array `a` lies inside a live PinnedBuffer."""
+    lo, hi = a.ctypes.data, a.ctypes.data + a.nbytes
+    return any(base <= lo and hi <= base + n for base, n in _PINNED.items())
+
+
+def _fixed_fmt(a):
+    """FMT_S8 / FMT_S16 for an int8 / int16 numpy array (the fixed-point capture formats), else None."""
+    if a.dtype.kind == "i" and a.dtype.itemsize == 1:
+        return FMT_S8
+    if a.dtype.kind == "i" and a.dtype.itemsize == 2:
+        return FMT_S16
+    return None
+
+
 class DevArray:
     """View of library-owned device memory for torch.as_tensor (via __cuda_array_interface__)."""
 
@@ -184,6 +202,9 @@ class SpectrumEngine:
         if getattr(self, "_h", None):
             lib.ksa_destroy(self._h)
             self._h = None
+        for buf in getattr(self, "_pinned", {}).values():
+            buf.close()
+        self._pinned = {}
 
     def __del__(self):
         try:
@@ -218,9 +239,47 @@ class SpectrumEngine:
             raise KsaError("block has %d samples, fullSize is %d" % (a.size, self.full_size))
         return np.ascontiguousarray(a, dtype=np.complex64), FMT_C64
 
+    # int8 / int16 I,Q from host memory.  The C ABI names its host-pointer entry points by format and has none for these two;
+    # page-locked memory from ksa_host_alloc is device-visible, so the block is handed to the `_dev` entry point as it is
+    # (staged into an engine-owned PinnedBuffer first unless it already lives in one) and the kernels read it over the host
+    # link.  Synchronises before returning: the contract of the host-pointer forms.
+    def _pinned_buf(self, name, nbytes):
+        bufs = self.__dict__.setdefault("_pinned", {})
+        buf = bufs.get(name)
+        if buf is None or buf.array.nbytes < nbytes:
+            if buf is not None:
+                self.synchronize()
+                buf.close()
+            buf = bufs[name] = PinnedBuffer((int(nbytes),), np.uint8)
+        return buf.array
+
+    def _fixed_blocks(self, a, what):
+        """int8 / int16 array [k][2*fullSize] -> (the same values in page-locked memory, fmt, k)."""
+        fmt, per = _fixed_fmt(a), 2 * self.full_size
+        if a.ndim != 2 or a.shape[1] != per:
+            raise KsaError("%s wants [k][%d] %s, got %s" % (what, per, a.dtype, a.shape))
+        a = np.ascontiguousarray(a, dtype=a.dtype.newbyteorder("<"))
+        if not _is_pinned(a):
+            dst = self._pinned_buf("iq", a.nbytes)[:a.nbytes].view(a.dtype).reshape(a.shape)
+            dst[...] = a
+            a = dst
+        return a, fmt, int(a.shape[0])
+
+    def _pinned_out(self, name, shape):
+        n = int(np.prod(shape)) * 4
+        return self._pinned_buf(name, n)[:n].view(np.float32).reshape(shape)
+
     def curscan(self, samples):
         """One captured block -> float64[fftSize] linear magnitudes, fftshifted (what sdr_curscan returns); with
-        cumu_mode PSD the Welch power density instead (what the reference's sdr_curscan returns under bUsePSD, K:383)."""
+        cumu_mode PSD the Welch power density instead (what the reference's sdr_curscan returns under bUsePSD, K:383).
+        complex64, uint8 I,Q or int8 / int16 I,Q (2*fullSize values)."""
+        a = np.asarray(samples)
+        if _fixed_fmt(a) is not None:
+            a, fmt, _ = self._fixed_blocks(a.reshape(1, -1), "curscan")
+            out = self._pinned_out("out", (self.fft_size,))
+            self.curscan_dev(a, fmt, 1, out)
+            self.synchronize()
+            return out.astype(np.float64)
         a, fmt = self._host_iq(samples)
         out = np.empty(self.fft_size, dtype=np.float32)
         fn = lib.ksa_curscan_u8 if fmt == FMT_U8 else lib.ksa_curscan_c64
@@ -233,6 +292,12 @@ class SpectrumEngine:
 
     # -- zeroSpan frame loop body (K:464-484) ------------------------------------------------------
     def frame(self, samples):
+        a = np.asarray(samples)
+        if _fixed_fmt(a) is not None:
+            a, fmt, _ = self._fixed_blocks(a.reshape(1, -1), "frame")
+            self.frames_dev(a, fmt, 1)
+            self.synchronize()
+            return
         a, fmt = self._host_iq(samples)
         fn = lib.ksa_frame_u8 if fmt == FMT_U8 else lib.ksa_frame_c64
         check(fn(self._h, _ptr(a)))
@@ -243,6 +308,13 @@ class SpectrumEngine:
         frames_dev on a device copy of the batch.  Returns (cur_db float32[k, N] or None, hm_rows float32[k, W] or None):
         the per-frame dB spectra and waterfall rows, each when asked for."""
         a = np.asarray(blocks)
+        if _fixed_fmt(a) is not None:      # int8 / int16 I,Q: [k][2*fullSize], read by the kernels from page-locked memory
+            a, fmt, k = self._fixed_blocks(a, "frames")
+            db = self._pinned_out("db", (k, self.fft_size)) if cur_db else None
+            rows = self._pinned_out("rows", (k, self.hm_width)) if hm_rows else None
+            self.frames_dev(a, fmt, k, first_index, total_frames, db, rows, commit)
+            self.synchronize()
+            return (None if db is None else db.copy()), (None if rows is None else rows.copy())
         if a.dtype == np.uint8:
             a, fn, per = np.ascontiguousarray(a), lib.ksa_frames_u8, 2 * self.full_size
         else:
@@ -347,6 +419,13 @@ class SpectrumEngine:
         """One pass from HOST memory (K:621-668 + K:696-697): blocks = [nsteps][fullSize] complex64, or
         [nsteps][2*fullSize] uint8 I,Q; staged through an engine-owned device buffer (ksa_scan_pass_c64 / _u8)."""
         a = np.asarray(blocks)
+        if _fixed_fmt(a) is not None:      # int8 / int16 I,Q: [nsteps][2*fullSize], read by the kernels from page-locked memory
+            a, fmt, k = self._fixed_blocks(a, "scan_pass")
+            if step_ok is not None and np.size(step_ok) != k:
+                raise KsaError("step_ok has %d entries for %d steps" % (np.size(step_ok), k))
+            self.scan_pass_dev(a, fmt, k, step_ok)
+            self.synchronize()
+            return
         if a.dtype == np.uint8:
             a, fn, per = np.ascontiguousarray(a), lib.ksa_scan_pass_u8, 2 * self.full_size
         else:
@@ -512,18 +591,21 @@ def scan_gather_state(engines, nsteps):
 
 
 class PinnedBuffer:
-    """Page-locked host memory from ksa_host_alloc as a numpy array (capture blocks copy faster from it)."""
+    """Page-locked host memory from ksa_host_alloc as a numpy array (capture blocks copy faster from it; it is device-visible
+    too, so `.array` may be handed to the `_dev` methods as the IQ pointer -- the route of int8 / int16 blocks)."""
 
     def __init__(self, shape, dtype):
         self.shape, self.dtype = tuple(int(x) for x in shape), np.dtype(dtype)
         nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         self._p = C.c_void_p()
         check(lib.ksa_host_alloc(C.byref(self._p), nbytes))
+        _PINNED[self._p.value] = nbytes
         self.array = np.frombuffer((C.c_char * nbytes).from_address(self._p.value), dtype=self.dtype).reshape(self.shape)
 
     def close(self):
         if getattr(self, "_p", None) and self._p.value:
             self.array = None
+            _PINNED.pop(self._p.value, None)
             lib.ksa_host_free(self._p)
             self._p = C.c_void_p()
 

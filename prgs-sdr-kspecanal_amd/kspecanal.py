@@ -10,7 +10,7 @@ mode words and aliases (K:816, K:912-921), the defaults (K:41-59), the dict `d` 
 with the same key names, the module-level `sdr_curscan(d)` seam that playback rebinds (K:531, K:543), and the
 arrays handed to matplotlib: d['Fft.Cur'|'Fft.Max'|'Fft.Min'|'Fft.Avg'], the freqs axis, and the
 [128, W] waterfall buffer (K:470-481, K:729).  New keys are additive: `source` (rtlsdr|synth|file:<path>),
-`device`, `iqFormat` (c64|u8), `frameBatch` (zeroSpan blocks per device call, default 1).  What moved to the GPU:
+`device`, `iqFormat` (c64|u8|s8|s16), `frameBatch` (zeroSpan blocks per device call, default 1).  What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
 refreshed once per pass (the whole pass is one device call) instead of once per tuned band, and in zeroSpan with
@@ -32,6 +32,7 @@ from . import engine as _engine
 from .engine import SpectrumEngine, KsaError, FMT_C64, FMT_U8
 from . import sources
 
+IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
 PLTCOMPRESS = ("MAX", "MIN", "AVG", "RAW", "CONV")
 
@@ -147,6 +148,8 @@ def handle_args(d, argv=None):
         prg_quit(d, "ERROR:handle_args: " + _engine.fft_size_message(d["fftSize"]))
     if d["curScanCumuMode"] not in ("AVG", "MAX", "MIN", "RAW", "PSD"):   # PSD: the Welch fold on the device (additive)
         prg_quit(d, "ERROR: Unknown cumuMode [{}], Quiting...".format(d["curScanCumuMode"]))
+    if d["iqFormat"] not in IQFORMATS:
+        prg_quit(d, "ERROR:handle_args: Unknown iqFormat [{}], expected one of {}".format(d["iqFormat"], "|".join(IQFORMATS)))
     if d["frameBatch"] < 1:
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] must be >= 1".format(d["frameBatch"]))
     if d["bUsePSD"] and d["frameBatch"] > 1:
@@ -172,12 +175,13 @@ def print_info(d):
 
 # ------------------------------------------------------------------------------------------ SDR seam
 def open_source(d):
-    """d['source']: rtlsdr (needs pyrtlsdr) | synth | file:<raw uint8 capture>."""
+    """d['source']: rtlsdr (needs pyrtlsdr) | synth | file:<raw capture: uint8 I,Q, or int8 / int16 I,Q under iqFormat s8 / s16>."""
     src = d["source"]
     if src == "synth":
         return sources.SyntheticSdr()
     if src.startswith("file:"):
-        return sources.FileSdr(src[5:], d["samplingRate"], d["centerFreq"])
+        fmt = d["iqFormat"] if d["iqFormat"] in ("s8", "s16") else "u8"
+        return sources.FileSdr(src[5:], d["samplingRate"], d["centerFreq"], iq_format=fmt)
     try:
         import rtlsdr
     except ImportError:
@@ -225,10 +229,30 @@ def sdr_setup(sdr, fC, fS, gain):
 SDR_READ_UNIT = 2 ** 18   # K:311
 
 
+def raw_format(d):
+    """What sdr_read's `raw` wants for d['iqFormat'] and d['sdr']: False (complex64 from read_samples), True (uint8 I,Q from
+    read_bytes) or "s8" / "s16" (int8 / int16 I,Q from read_iq) -- the raw forms only when the source can deliver them."""
+    fmt = d.get("iqFormat")
+    if fmt == "u8":
+        return hasattr(d["sdr"], "read_bytes")
+    if fmt in ("s8", "s16") and hasattr(d["sdr"], "read_iq"):
+        return fmt
+    return False
+
+
+def raw_dtype(raw):
+    """dtype and values per sample of the blocks sdr_read(..., raw) returns."""
+    if raw in ("s8", "s16"):
+        return sources.IQ_FORMATS[raw][0], 2
+    return (np.dtype(np.uint8), 2) if raw else (np.dtype(np.complex64), 1)
+
+
 def sdr_read(sdr, length, raw=False):
     """K:312-347, same signature (+ raw): one capture block in <= 2^18-sample reads.  Returns complex64, or -- raw=True and a
-    source that can deliver bytes -- uint8 I,Q pairs (the unpack then runs on the GPU)."""
-    raw = raw and hasattr(sdr, "read_bytes")
+    source that can deliver bytes -- uint8 I,Q pairs, or -- raw "s8" / "s16" and a source with read_iq -- int8 / int16 I,Q
+    pairs (the unpack then runs on the GPU)."""
+    fixed = raw if raw in ("s8", "s16") and hasattr(sdr, "read_iq") else None
+    raw = raw is True and hasattr(sdr, "read_bytes")
     parts, left = [], int(length)
     while left > 0:
         n = min(left, SDR_READ_UNIT)
@@ -236,7 +260,9 @@ def sdr_read(sdr, length, raw=False):
             want = int(2 ** np.ceil(np.log2(n)))      # K:343: the dongle only reads power-of-two sizes
         else:
             want = n
-        if raw:
+        if fixed:
+            parts.append(np.asarray(sdr.read_iq(want, fixed), dtype=sources.IQ_FORMATS[fixed][0])[:2 * n])
+        elif raw:
             parts.append(np.asarray(sdr.read_bytes(2 * want), dtype=np.uint8)[:2 * n])
         else:
             parts.append(np.asarray(sdr.read_samples(want))[:n].astype(np.complex64))
@@ -276,7 +302,9 @@ def psd_crosscheck(d, samples, mag):
     n, win = d["fftSize"], np.asarray(d["theWin"], dtype=np.float64)
     x = np.asarray(samples)
     if x.dtype == np.uint8:
-        x = (x[0::2].astype(np.float64) - 127.5) / 127.5 + 1j * ((x[1::2].astype(np.float64) - 127.5) / 127.5)
+        x = sources.unpack(x, "u8")
+    elif x.dtype == np.int8 or x.dtype == np.int16:
+        x = sources.unpack(x, "s8" if x.dtype == np.int8 else "s16")
     pxx, _ = mlab.psd(x.astype(np.complex128), NFFT=n, window=win, noverlap=int(n * (1 - d["curScanNonOverlap"])))
     if d["curScanCumuMode"] == "PSD":      # the device folded the same Welch PSD: like is compared with like
         amp = pxx
@@ -292,7 +320,7 @@ def psd_crosscheck(d, samples, mag):
 def sdr_curscan(d):
     """Drop-in for K:351-397: float64[fftSize], fftshifted -- linear magnitudes, or under curScanCumuMode PSD the linear
     Welch PSD (what K:383 returns under bUsePSD)."""
-    samples = sdr_read(d["sdr"], d["fullSize"], raw=d.get("iqFormat") == "u8")
+    samples = sdr_read(d["sdr"], d["fullSize"], raw=raw_format(d))
     mag = get_engine(d).curscan(samples)
     if d["bUsePSD"]:
         psd_crosscheck(d, samples, mag)
@@ -599,7 +627,7 @@ def _zero_span_frames(d, eng, freqs):
         eng.set_flags(d["bDataMax"], d["bDataMin"], d["bDataAvg"])          # GUI toggles K:471-476
         if sdr_curscan is _gpu_curscan and not d["bUsePSD"]:
             try:
-                eng.frame(sdr_read(d["sdr"], d["fullSize"], raw=d.get("iqFormat") == "u8"))   # fused K:464-484
+                eng.frame(sdr_read(d["sdr"], d["fullSize"], raw=raw_format(d)))   # fused K:464-484
             except EOFError:
                 prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)
         else:
@@ -617,12 +645,14 @@ def _zero_span_frames(d, eng, freqs):
 
 def _zero_span_batches(d, eng, freqs, batch):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
-    (ksa_frames_c64 / _u8); flags, the progress line and the plot refresh come once per batch.  prgLoopCnt still counts
+    (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
+    line and the plot refresh come once per batch.  prgLoopCnt still counts
     frames, and a source that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of
     frameBatch 1."""
-    u8 = d.get("iqFormat") == "u8" and hasattr(d["sdr"], "read_bytes")      # what sdr_read(..., raw) delivers
+    u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
     full = d["fullSize"]
-    stage = _engine.PinnedBuffer((batch, 2 * full) if u8 else (batch, full), np.uint8 if u8 else np.complex64)
+    dtype, per = raw_dtype(u8)
+    stage = _engine.PinnedBuffer((batch, per * full), dtype)
     blocks = stage.array
     read_blocks = getattr(d["sdr"], "read_blocks", None)
     try:
@@ -730,9 +760,11 @@ def scan_range(d):
     eng.scan_set_base_is_raw(d["bScanRangeBaseDataIsRaw"])
     span = groups * d["samplingRate"]
     d["freqsAll"] = np.fft.fftshift(np.fft.fftfreq(total, 1 / span) + d["startFreq"] + span / 2)   # K:609
-    u8 = d["iqFormat"] == "u8" and hasattr(d["sdr"], "read_bytes")
-    # one pass of capture blocks in page-locked host memory; the library stages it to the GPU (ksa_scan_pass_c64 / _u8)
-    stage = _engine.PinnedBuffer((steps, d["fullSize"] * 2) if u8 else (steps, d["fullSize"]), np.uint8 if u8 else np.complex64)
+    u8 = raw_format(d)
+    # one pass of capture blocks in page-locked host memory; the library stages it to the GPU (ksa_scan_pass_c64 / _u8), or the
+    # kernels read it from there (int8 / int16 I,Q: ksa_scan_pass_dev)
+    dtype, per = raw_dtype(u8)
+    stage = _engine.PinnedBuffer((steps, per * d["fullSize"]), dtype)
     blocks = stage.array
     d["fftHM"], d["fftHMIndex"] = eng.hm_rows(0, _engine.HM_ROWS, scan=True), 0    # K:613-614, read once
     prev = time.time()

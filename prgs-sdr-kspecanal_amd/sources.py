@@ -6,9 +6,37 @@ Anything with that surface can be plugged in.  Two sources ship here because the
 dongle: a synthetic tone generator (the role of the reference's python/testfft.py, written for
 numpy >= 2) and a reader for raw `rtl_sdr` uint8 captures (octave/load_rtlsdr.m:8-12,
 octave/hkvc-dump_samples.sh:6).  Both can hand over uint8 I,Q pairs (`read_bytes`) so that the unpack
-runs on the GPU (row A0).
+runs on the GPU (row A0).  Captures also come as interleaved signed int8 (HackRF, SigMF ci8: b / 128) and little-endian
+int16 (USRP, SigMF ci16_le, Airspy, SDRplay: b / 32768): `read_iq(n, fmt)` hands those over in their own dtype, again for
+the GPU to unpack.
 """
 import numpy as np
+
+# iqFormat -> (dtype of one I or Q value, the unpack to [-1, 1): (b - offset) / scale)
+IQ_FORMATS = {"u8": (np.dtype(np.uint8), 127.5, 127.5), "s8": (np.dtype(np.int8), 0.0, 128.0),
+              "s16": (np.dtype("<i2"), 0.0, 32768.0)}
+
+
+def quantise(x, fmt):
+    """Complex samples -> interleaved I,Q in the capture format `fmt`: clip(round((x+1)*127.5)) as the dongle delivers them,
+    clip(round(x*127), -128, 127) for s8, clip(round(x*32767), -32768, 32767) for s16."""
+    dtype = IQ_FORMATS[fmt][0]
+    out = np.empty(2 * len(x), dtype=dtype)
+    for part, v in ((0, x.real), (1, x.imag)):
+        if fmt == "u8":
+            out[part::2] = np.clip(np.round((v + 1.0) * 127.5), 0, 255)
+        elif fmt == "s8":
+            out[part::2] = np.clip(np.round(v * 127), -128, 127)
+        else:
+            out[part::2] = np.clip(np.round(v * 32767), -32768, 32767)
+    return out
+
+
+def unpack(b, fmt):
+    """Interleaved I,Q of format `fmt` (last axis) -> complex128, the documented unpack of that format."""
+    _, offset, scale = IQ_FORMATS[fmt]
+    b = b.astype(np.float64)
+    return (b[..., 0::2] - offset) / scale + 1j * ((b[..., 1::2] - offset) / scale)
 
 
 class _SdrBase:
@@ -55,25 +83,31 @@ class SyntheticSdr(_SdrBase):
 
     def read_bytes(self, nbytes):
         """uint8 I,Q interleaved, as the dongle delivers them (clip(round((x+1)*127.5)))."""
-        x = self.read_samples(int(nbytes) // 2)
-        out = np.empty(2 * len(x), dtype=np.uint8)
-        out[0::2] = np.clip(np.round((x.real + 1.0) * 127.5), 0, 255)
-        out[1::2] = np.clip(np.round((x.imag + 1.0) * 127.5), 0, 255)
-        return out
+        return quantise(self.read_samples(int(nbytes) // 2), "u8")
+
+    def read_iq(self, n, fmt):
+        """n samples as interleaved I,Q of format `fmt` (u8 | s8 | s16), 2*n values of that format's dtype."""
+        return quantise(self.read_samples(int(n)), fmt)
 
 
 class FileSdr(_SdrBase):
-    """Replays a raw `rtl_sdr -n ... file.bin` capture: interleaved uint8 I,Q.  read_samples applies the
-    documented unpack (b - 127.5)/127.5; read_bytes hands the bytes to the GPU unpack untouched.
-    At end of file it raises EOFError (the reference's playback path treats any load failure as
+    """Replays a raw `rtl_sdr -n ... file.bin` capture: interleaved uint8 I,Q -- or, with iq_format s8 / s16, a capture of
+    interleaved signed int8 / little-endian int16 I,Q.  read_samples applies the documented unpack ((b - 127.5)/127.5, b / 128,
+    b / 32768); read_bytes hands the file's bytes over untouched and read_iq the same bytes in the format's dtype, for the GPU
+    unpack.  At end of file it raises EOFError (the reference's playback path treats any load failure as
     end of stream, python/kspecanal.py:559-563)."""
 
-    def __init__(self, path, sample_rate=2.4e6, center_freq=92e6, loop=False):
+    def __init__(self, path, sample_rate=2.4e6, center_freq=92e6, loop=False, iq_format="u8"):
         super().__init__()
+        if iq_format not in IQ_FORMATS:
+            raise ValueError("FileSdr: unknown iq_format [%s] (u8 | s8 | s16)" % iq_format)
         self.sample_rate, self.center_freq = sample_rate, center_freq
         self._raw = np.memmap(path, dtype=np.uint8, mode="r")
         self._pos = 0
         self.loop = loop
+        self.iq_format = iq_format
+        self._dtype = IQ_FORMATS[iq_format][0]
+        self._bps = 2 * self._dtype.itemsize               # bytes per IQ sample
 
     def read_bytes(self, nbytes):
         nbytes = int(nbytes)
@@ -85,32 +119,36 @@ class FileSdr(_SdrBase):
         self._pos += nbytes
         return out
 
-    def read_samples(self, n):
-        b = self.read_bytes(2 * int(n)).astype(np.float64)
-        return (b[0::2] - 127.5) / 127.5 + 1j * ((b[1::2] - 127.5) / 127.5)
+    def read_iq(self, n, fmt=None):
+        """n samples of the capture untouched: 2*n values of the capture format's dtype."""
+        if fmt is not None and fmt != self.iq_format:
+            raise ValueError("FileSdr: the capture is %s, not %s" % (self.iq_format, fmt))
+        return self.read_bytes(self._bps * int(n)).view(self._dtype)
 
-    @staticmethod
-    def _unpack(b):
-        b = b.astype(np.float64)
-        return (b[..., 0::2] - 127.5) / 127.5 + 1j * ((b[..., 1::2] - 127.5) / 127.5)
+    def read_samples(self, n):
+        return unpack(self.read_iq(n), self.iq_format)
+
+    def _unpack(self, b):
+        return unpack(b.view(self._dtype), self.iq_format)
 
     def read_blocks(self, k, length, raw, out):
         """Fill out[:k] exactly as k calls of kspecanal.sdr_read(self, length, raw) would: the same bytes consumed (reads of at
-        most 2^18 samples, a short tail read rounded up to a power of two and cut back, K:343) and the same values (uint8 I,Q, or
-        complex64 through read_samples' unpack).  Returns the number of whole blocks read before the end of the capture."""
+        most 2^18 samples, a short tail read rounded up to a power of two and cut back, K:343) and the same values (the
+        capture's own uint8 / int8 / int16 I,Q, or complex64 through read_samples' unpack).  Returns the number of whole blocks
+        read before the end of the capture."""
         k, length = int(k), int(length)
         unit = 2 ** 18                                     # kspecanal.SDR_READ_UNIT, K:311
         parts = [unit] * (length // unit) + ([length % unit] if length % unit else [])
         wants = [n if n >= unit else int(2 ** np.ceil(np.log2(n))) for n in parts]
-        per = 2 * sum(wants)                               # bytes one block consumes
+        per = self._bps * sum(wants)                       # bytes one block consumes
         done = 0
-        if per == 2 * length and not self.loop:
+        if per == self._bps * length and not self.loop:
             # every read is used whole: the blocks are back to back in the capture, one slice per group of blocks
             whole = min(k, (len(self._raw) - self._pos) // per)
             for g in range(0, whole, 64):
                 m = min(64, whole - g)
                 src = self._raw[self._pos:self._pos + m * per].reshape(m, per)
-                out[g:g + m] = src if raw else self._unpack(src)
+                out[g:g + m] = src.view(self._dtype) if raw else self._unpack(src)
                 self._pos += m * per
             done = whole
         for i in range(done, k):                          # read by read, as sdr_read does (end of file, loop)
@@ -118,7 +156,7 @@ class FileSdr(_SdrBase):
                 col = 0
                 for n, want in zip(parts, wants):
                     if raw:
-                        out[i, 2 * col:2 * (col + n)] = self.read_bytes(2 * want)[:2 * n]
+                        out[i, 2 * col:2 * (col + n)] = self.read_iq(want)[:2 * n]
                     else:
                         out[i, col:col + n] = self.read_samples(want)[:n]
                     col += n

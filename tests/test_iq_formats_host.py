@@ -1,0 +1,196 @@
+"""CPU side of the int8 / int16 IQ formats (KSA_FMT_S8 = 2, KSA_FMT_S16 = 3): the header, the binding and the package agree
+and the ABI is untouched (5, 52 entry points); FileSdr / SyntheticSdr deliver both formats with the documented quantisers and
+unpacks; FileSdr.read_blocks consumes the same bytes as repeated sdr_read; the front end accepts `iqFormat s8|s16` and
+refuses a value it does not know."""
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, load_pkg
+
+FORMATS = {"s8": (np.int8, 128.0, 2), "s16": (np.dtype("<i2"), 32768.0, 4)}   # dtype, divisor, bytes per IQ sample
+
+
+def _k():
+    load_pkg()
+    return importlib.import_module("prgs-sdr-kspecanal_amd.kspecanal")
+
+
+def _src():
+    load_pkg()
+    return importlib.import_module("prgs-sdr-kspecanal_amd.sources")
+
+
+# ------------------------------------------------------------------------------------------------ header / binding / package
+def test_header_binding_and_package_agree_and_the_abi_is_untouched():
+    pkg = load_pkg()
+    lib = importlib.import_module("prgs-sdr-kspecanal_amd._lib")
+    hdr = open(os.path.join(ROOT, "include", "ksa.h")).read()
+    enums = dict((k, int(v)) for k, v in re.findall(r"\b(KSA_FMT_\w+)\s*=\s*(\d+)", hdr))
+    assert enums == {"KSA_FMT_C64": 0, "KSA_FMT_U8": 1, "KSA_FMT_S8": 2, "KSA_FMT_S16": 3}
+    assert (lib.FMT_C64, lib.FMT_U8, lib.FMT_S8, lib.FMT_S16) == (0, 1, 2, 3)
+    for name in ("FMT_S8", "FMT_S16"):
+        assert getattr(pkg, name) == getattr(lib, name) and name in pkg.__all__
+    assert int(re.search(r"#define\s+KSA_ABI_VERSION\s+(\d+)", hdr).group(1)) == 5 == lib.ABI_VERSION
+    assert lib.lib.ksa_abi_version() == 5
+    assert len(lib.SIGNATURES) == 52
+    # every `ksa_name(` token of the header is still one of the 52 declared entry points (comments included)
+    assert set(re.findall(r"\b(ksa_\w+)\s*\(", hdr)) == set(lib.SIGNATURES)
+    # the header says what an older library does with the new values, and that pinned memory is a valid IQ pointer
+    assert "unknown sample format" in hdr and re.search(r"ksa_host_alloc[^;]*?`_dev` entry points", hdr, flags=re.S)
+
+
+def test_the_library_knows_the_sample_sizes_and_instantiates_every_load_stage():
+    src = open(os.path.join(ROOT, "prgs-sdr-kspecanal_amd", "csrc", "ksa_api.hip")).read()
+    assert re.search(r"size_t sample_bytes\(int fmt\) \{ return fmt == KSA_FMT_C64 \? 8 : fmt == KSA_FMT_S16 \? 4 : 2; \}", src)
+    for needle in ("launch_spec_n<ksa::FMT_S8>(e, dummy, true)", "launch_spec_n<ksa::FMT_S16>(e, dummy, true)",
+                   "launch_mr<ksa::FMT_S8>(e, dummy, true)", "launch_mr<ksa::FMT_S16>(e, dummy, true)",
+                   "dif16_kernel<ksa::FMT_S8>", "dif16_kernel<ksa::FMT_S16>", "dif_wide_kernel<ksa::FMT_S8, 32>",
+                   "dif_wide_kernel<ksa::FMT_S16, 32>", "dif_wide_kernel<ksa::FMT_S8, 64>", "dif_wide_kernel<ksa::FMT_S16, 64>"):
+        assert needle in src, needle
+
+
+# ------------------------------------------------------------------------------------------------ sources
+@pytest.mark.parametrize("fmt", ["s8", "s16"])
+def test_synthetic_source_quantises_as_documented(fmt):
+    S = _src()
+    dtype, div, _ = FORMATS[fmt]
+    a, b = S.SyntheticSdr(seed=5), S.SyntheticSdr(seed=5)
+    got = a.read_iq(4096, fmt)
+    x = b.read_samples(4096)
+    top = 127 if fmt == "s8" else 32767
+    want = np.empty(8192, dtype=dtype)
+    want[0::2] = np.clip(np.round(x.real * top), -top - 1, top)
+    want[1::2] = np.clip(np.round(x.imag * top), -top - 1, top)
+    assert got.dtype == np.dtype(dtype) and np.array_equal(got, want)
+    # the extremes clip instead of wrapping
+    big = np.array([2.0 + 2.0j, -2.0 - 2.0j, 1.0 - 1.0j])
+    q = S.quantise(big, fmt)
+    assert q.tolist() == [top, top, -top - 1, -top - 1, top, -top]
+    # the uint8 form is what it was
+    c, d = S.SyntheticSdr(seed=6), S.SyntheticSdr(seed=6)
+    y = d.read_samples(1000)
+    u8 = np.empty(2000, dtype=np.uint8)
+    u8[0::2] = np.clip(np.round((y.real + 1.0) * 127.5), 0, 255)
+    u8[1::2] = np.clip(np.round((y.imag + 1.0) * 127.5), 0, 255)
+    assert np.array_equal(c.read_bytes(2000), u8)
+
+
+@pytest.mark.parametrize("fmt", ["s8", "s16"])
+def test_file_source_round_trip(tmp_path, fmt):
+    """A capture written from the synthetic quantiser comes back value for value: read_iq in the capture's dtype, read_bytes
+    as the file's bytes, read_samples through the documented unpack (b / 128, b / 32768)."""
+    S = _src()
+    dtype, div, bps = FORMATS[fmt]
+    raw = S.SyntheticSdr(seed=8).read_iq(3000, fmt)
+    lo, hi = np.iinfo(dtype).min, np.iinfo(dtype).max
+    raw[:4] = (lo, hi, hi, lo)
+    path = tmp_path / ("cap.%s" % fmt)
+    raw.astype(dtype).tofile(path)
+    f = S.FileSdr(str(path), iq_format=fmt)
+    a = f.read_iq(1000)
+    assert a.dtype == np.dtype(dtype) and np.array_equal(a, raw[:2000])
+    b = f.read_bytes(bps * 500)
+    assert b.dtype == np.uint8 and np.array_equal(b.view(dtype), raw[2000:3000])
+    x = f.read_samples(1500)
+    want = raw[3000:].astype(np.float64) / div
+    assert np.array_equal(x.real, want[0::2]) and np.array_equal(x.imag, want[1::2])
+    assert f._pos == bps * 3000
+    with pytest.raises(EOFError):
+        f.read_samples(1)
+    with pytest.raises(ValueError):
+        S.FileSdr(str(path), iq_format="u8").read_iq(10, fmt)
+    with pytest.raises(ValueError):
+        S.FileSdr(str(path), iq_format="s12")
+    # the unpack of the extremes
+    g = S.FileSdr(str(path), iq_format=fmt)
+    y = g.read_samples(2)
+    assert y[0] == complex(-1.0, hi / div) and y[1] == complex(hi / div, -1.0)
+    # the existing signature and the uint8 unpack keep working
+    u = np.arange(256, dtype=np.uint8)
+    upath = tmp_path / "cap.u8"
+    u.tofile(upath)
+    h = S.FileSdr(str(upath), 2.4e6, 92e6, False)
+    z = h.read_samples(128)
+    assert np.array_equal(z.real, (u[0::2].astype(np.float64) - 127.5) / 127.5)
+
+
+@pytest.mark.parametrize("length", [2 ** 14, 2 ** 18 + 12345, 1000])
+@pytest.mark.parametrize("raw", [True, False])
+@pytest.mark.parametrize("fmt", ["s8", "s16"])
+def test_read_blocks_equals_repeated_sdr_read(tmp_path, fmt, length, raw):
+    """As the uint8 test of test_host_frames.py: byte for byte and value for value, the power-of-two rounding of a short tail
+    read and a capture that ends inside the last block included."""
+    K, S = _k(), _src()
+    dtype, div, bps = FORMATS[fmt]
+    k = 5
+    per = bps * sum(n if n >= 2 ** 18 else int(2 ** np.ceil(np.log2(n)))
+                    for n in [2 ** 18] * (length // 2 ** 18) + ([length % 2 ** 18] if length % 2 ** 18 else []))
+    for nbytes, whole in ((per * k + 8, k), (per * 3 + per // 2, 3)):
+        data = np.random.default_rng(length % 1000 + whole).integers(0, 256, nbytes, dtype=np.uint8)
+        path = tmp_path / ("cap%d_%d.bin" % (length, whole))
+        data.tofile(path)
+        a, b = S.FileSdr(str(path), iq_format=fmt), S.FileSdr(str(path), iq_format=fmt)
+        shape, dt = ((k, 2 * length), dtype) if raw else ((k, length), np.complex64)
+        out = np.zeros(shape, dtype=dt)
+        got = a.read_blocks(k, length, fmt if raw else False, out)
+        want = []
+        try:
+            for _ in range(k):
+                want.append(K.sdr_read(b, length, raw=fmt if raw else False))
+        except EOFError:
+            pass
+        assert got == len(want) == whole
+        assert a._pos == b._pos, "bytes consumed differ"
+        for i in range(got):
+            assert out[i].dtype == want[i].dtype and np.array_equal(out[i], want[i]), i
+        if raw and whole == k and per == bps * length:
+            assert np.array_equal(out.reshape(-1), data[:per * k].view(dtype))
+
+
+# ------------------------------------------------------------------------------------------------ front end
+@pytest.mark.parametrize("fmt", ["s8", "s16", "S16", "u8", "c64"])
+def test_handle_args_accepts_the_formats(fmt):
+    K = _k()
+    d = K.handle_args({"cmd.stop": False}, ["zeroSpan", "iqFormat", fmt, "source", "synth", "frameBatch", "8"])
+    assert d["iqFormat"] == fmt.lower() and d["cmd.stop"] is False
+    d = K.handle_args({"cmd.stop": False}, ["scan", "startFreq", "99e6", "endFreq", "106e6", "iqFormat", fmt, "curScanCumuMode", "psd"])
+    assert d["iqFormat"] == fmt.lower() and d["curScanCumuMode"] == "PSD"
+
+
+def test_handle_args_refuses_an_unknown_format_and_names_the_key(capsys):
+    K = _k()
+    with pytest.raises(SystemExit):
+        K.handle_args({"cmd.stop": False}, ["zeroSpan", "iqFormat", "bogus"])
+    out = capsys.readouterr().out
+    assert "iqFormat" in out and "bogus" in out, out
+
+
+@pytest.mark.parametrize("fmt", ["s8", "s16"])
+def test_sdr_read_hands_over_the_native_dtype_and_open_source_passes_the_format(tmp_path, fmt):
+    K, S = _k(), _src()
+    dtype, div, bps = FORMATS[fmt]
+    raw = S.SyntheticSdr(seed=3).read_iq(5000, fmt)
+    path = tmp_path / "cap.bin"
+    raw.tofile(path)
+    d = K.handle_args({"cmd.stop": False}, ["zeroSpan", "iqFormat", fmt, "source", "file:%s" % path])
+    sdr = K.open_source(d)
+    assert sdr.iq_format == fmt
+    d["sdr"] = sdr
+    assert K.raw_format(d) == fmt
+    blk = K.sdr_read(sdr, 3000, raw=fmt)          # 3000 -> one read of 4096 samples, cut back (K:343)
+    assert blk.dtype == np.dtype(dtype) and np.array_equal(blk, raw[:6000]) and sdr._pos == bps * 4096
+    # a source that cannot deliver the format falls back to complex64 from read_samples, as `u8` does
+
+    class Plain:
+        def read_samples(self, n):
+            return np.zeros(n, dtype=np.complex128)
+
+    d["sdr"] = Plain()
+    assert K.raw_format(d) is False and K.sdr_read(d["sdr"], 64, raw=fmt).dtype == np.complex64
+    # under iqFormat c64 / u8 a file is the uint8 capture it always was
+    d2 = K.handle_args({"cmd.stop": False}, ["zeroSpan", "iqFormat", "u8", "source", "file:%s" % path])
+    assert K.open_source(d2).iq_format == "u8"
