@@ -44,6 +44,24 @@ enum { KSA_CUMU_RAW = 0, KSA_CUMU_AVG = 1, KSA_CUMU_MAX = 2, KSA_CUMU_MIN = 3 };
  * that runs the spectrum stage accepts it.  The layout and the calls are unchanged, so the ABI number is too: a library
  * without this fold refuses it in ksa_create ("unknown cumu_mode 4"). */
 enum { KSA_CUMU_PSD = 4 };
+/* Polyphase filter bank front end (weighted overlap-add; the reference has no counterpart).  Per captured block
+ *   y[n]     = sum over k < num_windows, in the order k = 0, 1, ..., of x[window_starts[k] + n] * window[k*fft_size + n]
+ *   out[bin] = mag_scale * |FFT_N(y)[bin]|                                                                   (fftshifted)
+ * num_windows is the tap count P, 1 <= P <= KSA_PFB_MAX_TAPS; window is host[P*fft_size] (the prototype filter, segment k at
+ * window + k*fft_size); window_starts are validated against full_size as for the other folds; mag_scale is the caller's
+ * (2 / sum(window) reads a unit tone at 2.0, the convention of K:373 / K:391 on the long window).  The segments are summed in
+ * the time domain and ONE transform runs per block: with window_starts[k] = k*fft_size and the `_dev` entry points'
+ * frame_stride = fft_size this is the critically sampled PFB spectrometer over a sample stream (frame f covers samples
+ * [f*N, (f+P)*N)).  full_size stays the caller's block length (staging and checks of the host-pointer entry points).
+ * KSA_OUT_DB / KSA_OUT_DB_CLIP apply as for the AVG fold.  A NaN sample makes every bin of its frame NaN; an all-zero block
+ * gives -inf dB (KSA_OUT_DB) or 0 (KSA_OUT_DB_CLIP, min_amp 0) as with the other folds.  Every fft_size, every sample format
+ * and every entry point that runs the spectrum stage accepts it; the state, the waterfall, the plot hand-off and the
+ * multi-engine merges consume per-frame spectra and are unchanged.  The transform stage is the engine's usual kernel for
+ * fft_size on complex64 frames of one all-ones window (what the path of the kernel-info entry point describes), whatever the
+ * input format.  The layout and the calls are unchanged, so the ABI number is too: a library without this fold refuses it in
+ * ksa_create ("unknown cumu_mode 5"). */
+enum { KSA_CUMU_PFB = 5 };
+#define KSA_PFB_MAX_TAPS 16
 /* IQ sample formats: complex64 (what sdr.read_samples hands over, narrowed from K:335's complex128)
  * and the dongle's native interleaved uint8 I,Q (pyrtlsdr packed_bytes_to_iq; K:301, K:339, K:346) */
 enum { KSA_FMT_C64 = 0, KSA_FMT_U8 = 1 };
@@ -72,9 +90,10 @@ typedef struct ksa_config {
                                    (the mixed-radix path; the layout and the calls are unchanged, so the ABI number is too:
                                    a library without that path refuses such sizes in ksa_create) */
   int32_t full_size;            /* d['fullSize'] K:926-929: samples per captured block */
-  int32_t num_windows;          /* windows actually transformed (K:385-390) */
+  int32_t num_windows;          /* windows actually transformed (K:385-390); KSA_CUMU_PFB: the tap count P */
   const int32_t* window_starts; /* host[num_windows]: iStart = int(i*fftSize*nonOverlap) K:386 */
-  const float* window;          /* host[fft_size]: d['theWin'] K:932-936 */
+  const float* window;          /* host[fft_size]: d['theWin'] K:932-936; the length depends on the mode: KSA_CUMU_PFB
+                                   reads host[num_windows*fft_size], the prototype filter */
   double mag_scale;             /* 2*winAdj/fftSize with winAdj = N/sum(win): K:373, K:391 */
   int32_t cumu_mode;            /* KSA_CUMU_*: within-block fold K:392-395 */
   float gain;                   /* d['gain'] subtracted by LogNoGain K:109 */
@@ -282,7 +301,8 @@ int ksa_host_free(void* p);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* HIP-event timing of the spectrum kernel on the engine's stream: enable, run, then read the sum
- * of kernel durations and the launch count since the last enable. */
+ * of kernel durations and the launch count since the last enable.  A KSA_CUMU_PFB engine profiles every fold + transform chunk
+ * of a call as a stage of its own (fold included): such a call adds one launch per chunk, and its clock stamps likewise. */
 int ksa_prof_enable(ksa_engine* e, int32_t on);
 int ksa_prof_read(ksa_engine* e, double* spectrum_ms, int64_t* launches);
 /* Shader clock the chip held under the profiled spectrum stages since the last ksa_prof_enable(1): a stamp kernel on

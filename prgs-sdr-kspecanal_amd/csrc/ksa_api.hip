@@ -19,6 +19,7 @@
 #include "ksa_kernels64.hpp"
 #include "ksa_kernels_pair.hpp"
 #include "ksa_kernels_mr.hpp"
+#include "ksa_pfb.hpp"
 
 namespace {
 
@@ -73,6 +74,14 @@ constexpr const char* exp_env(const char*) { return nullptr; }
 // default first-stage scratch per chunk of frames (ksa_dif16.hpp); tuned on MI355X, see DESIGN.md 4.2
 #ifndef KSA_DIF_SCRATCH_MB_DEFAULT
 #define KSA_DIF_SCRATCH_MB_DEFAULT 4096
+#endif
+
+// KSA_CUMU_PFB: bytes of folded frames (complex64 [frames][N]) that one fold + transform chunk holds in engine scratch: the
+// bound of that scratch.  Measured at 16 / 64 / 256 MiB (profiles/pfb_sweep.txt): the larger the faster -- every chunk is a fold
+// launch and a transform launch that drain one after the other, which keeping a chunk inside the last-level cache does not
+// pay back.
+#ifndef KSA_PFB_CHUNK_BYTES
+#define KSA_PFB_CHUNK_BYTES (256ll << 20)
 #endif
 
 // host mirrors of ksa::Tune<N>::FUSED / FUSED_LAST (the twiddle table layouts depend on them)
@@ -152,6 +161,13 @@ struct ksa_engine {
   int* d_starts_b = nullptr;    // [nwin] w*N1
   int dif_chunk = 1;
   int dif_radix = 16;           // first-stage radix: 16 (N <= 262144), 32 (524288), 64 (1048576)
+  // KSA_CUMU_PFB (ksa_pfb.hpp): the fold's tables and its output.  d_starts / d_window then hold the transform stage's inner
+  // shape (one window at 0, all-ones taps); cfg keeps the caller's outer shape (full_size, num_windows = taps).
+  int* d_pfb_starts = nullptr;  // [P] the caller's window_starts
+  float* d_pfb_taps = nullptr;  // [P][N] the caller's window
+  float2* d_pfb_y = nullptr;    // [pfb_chunk][N] folded frames
+  int pfb_chunk = 0;            // frames per fold + transform chunk (a multiple of 4)
+  bool pfb_ring_ok = false;     // starts[k] == k*N and P in {4, 8, 16}: the ring kernel may serve frame_stride == N
   // bookkeeping
   long long frames_seen = 0;
   int hm_index = 0;
@@ -196,6 +212,8 @@ int plan_of(const ksa_engine* e, const SpecParams& p) { return std::max(p.nframe
 // KSA_CUMU_PSD engines run the CUMU_PSD instantiation of every spectrum kernel (a template constant everywhere, also where the
 // other folds branch at run time) with SpecParams::cumu = CUMU_AVG: the combines and the output stage of the two are the same.
 bool fold_psd(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PSD; }
+// KSA_CUMU_PFB engines fold in the time domain (ksa_pfb.hpp) and run the AVG instantiations on one window per folded frame.
+bool fold_pfb(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PFB; }
 size_t sample_bytes(int fmt);   // bytes per IQ sample of a KSA_FMT_* value
 
 template <int N, int FMT, int RM, int CM>
@@ -517,6 +535,58 @@ int plan_mr(int n, ksa::MrPlan* plan, int* threads, std::vector<float2>* tw) {
   return fail("fft_size %d needs more than %d threads", n, ksa::MR_MAX_THREADS);
 }
 
+// One fold launch of a KSA_CUMU_PFB engine: `nframes` frames of the caller's samples -> d_pfb_y[nframes][N].
+struct PfbFold {
+  const void* iq;       // first frame of the chunk
+  int fmt;
+  long long stride;     // samples between frames
+  int nframes;          // <= pfb_chunk
+};
+
+template <int FMT>
+int launch_pfb_fmt(ksa_engine* e, const ksa::PfbParams& a, bool ring) {
+  const long long per = a.n / ksa::PFB_COLS;
+  if (ring) {
+    const long long items = per * ((a.nframes + ksa::PFB_SLICE_FRAMES - 1) / ksa::PFB_SLICE_FRAMES);
+    const dim3 grid((unsigned)((items + ksa::PFB_THREADS - 1) / ksa::PFB_THREADS));
+    // (only the (format, P) pairs the rule below can select are instantiated: ksa::pfb_ring_pays)
+    if constexpr (ksa::pfb_ring_pays(FMT, 4)) {
+      if (a.ntaps == 4) hipLaunchKernelGGL((ksa::pfb_ring_kernel<FMT, 4>), grid, dim3(ksa::PFB_THREADS), 0, e->stream, a);
+    }
+    if (a.ntaps == 8) hipLaunchKernelGGL((ksa::pfb_ring_kernel<FMT, 8>), grid, dim3(ksa::PFB_THREADS), 0, e->stream, a);
+    if (a.ntaps == 16) hipLaunchKernelGGL((ksa::pfb_ring_kernel<FMT, 16>), grid, dim3(ksa::PFB_THREADS), 0, e->stream, a);
+  } else {
+    const long long items = per * a.nframes;
+    const long long blocks = (items + ksa::PFB_THREADS - 1) / ksa::PFB_THREADS;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)e->num_cu * 32)));
+    hipLaunchKernelGGL(ksa::pfb_fold_kernel<FMT>, grid, dim3(ksa::PFB_THREADS), 0, e->stream, a);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_pfb(ksa_engine* e, const PfbFold& f) {
+  const ksa_config& c = e->cfg;
+  ksa::PfbParams a{};
+  a.iq = f.iq;
+  a.frame_stride = f.stride;
+  a.nframes = f.nframes;
+  a.n = c.fft_size;
+  a.ntaps = c.num_windows;
+  a.starts = e->d_pfb_starts;
+  a.taps = e->d_pfb_taps;
+  a.u8_offset = c.u8_offset;
+  a.u8_inv_scale = 1.0f / c.u8_scale;
+  a.y = e->d_pfb_y;
+  // The ring kernel where it measured faster than the generic one at stride N (profiles/pfb_sweep.txt): it saves (P - 1)
+  // re-reads of a sample per output point and pays with P - 1 warm-up loads per slice and fewer, longer threads; from 12 saved
+  // bytes up it won (complex64 P >= 4, 2-byte samples P >= 8), below that the generic kernel's re-reads hit in cache and it lost.
+  // (KSA_PFB_NO_RING: A/B switch of the experiments build.)
+  const bool ring = e->pfb_ring_ok && f.stride == c.fft_size && ksa::pfb_ring_pays(f.fmt, c.num_windows) && !exp_env("KSA_PFB_NO_RING");
+  return f.fmt == KSA_FMT_C64 ? launch_pfb_fmt<ksa::FMT_C64>(e, a, ring) : f.fmt == KSA_FMT_S8 ? launch_pfb_fmt<ksa::FMT_S8>(e, a, ring)
+         : f.fmt == KSA_FMT_S16 ? launch_pfb_fmt<ksa::FMT_S16>(e, a, ring) : launch_pfb_fmt<ksa::FMT_U8>(e, a, ring);
+}
+
 int prof_begin(ksa_engine* e, hipEvent_t* a, hipEvent_t* b) {
   *a = *b = nullptr;
   if (!e->prof || e->prof_events.size() >= 8192) return 0;
@@ -619,8 +689,8 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int 
 // Spectrum stage for a batch: the single-workgroup LDS FFT, behind a radix-16 / 32 / 64 first stage for N > 16384.
 // The call transforms frames [batch_first, batch_first + nframes) of a batch of batch_frames (0: nframes) and takes the
 // whole batch's launch plan, ring rows and ring window: slot by slot it writes what one call over the batch writes.
-int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, int out_mode,
-                 float* out, bool with_hm, float* hm_rows, int batch_first = 0, int batch_frames = 0) {
+// What every spectrum-stage call checks on the samples it is handed (the caller's, or a chunk of folded frames).
+int check_frames(const ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, const float* out, const float* hm_rows) {
   const ksa_config& c = e->cfg;
   if (fmt != KSA_FMT_C64 && fmt != KSA_FMT_U8 && fmt != KSA_FMT_S8 && fmt != KSA_FMT_S16) return fail("unknown sample format %d", fmt);
   if (nframes < 1 || nframes > c.max_frames) return fail("nframes %d outside 1..max_frames(%d)", nframes, c.max_frames);
@@ -630,13 +700,21 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   if ((reinterpret_cast<uintptr_t>(out) & 15) || (hm_rows && (reinterpret_cast<uintptr_t>(hm_rows) & 15)))
     return fail("device output buffers must be 16-byte aligned");
   if (reinterpret_cast<uintptr_t>(iq) & (sample_bytes(fmt) - 1)) return fail("IQ buffer is not sample aligned");
+  return 0;
+}
+
+// `fold` (KSA_CUMU_PFB): the fold launch that fills `iq` for these frames, enqueued inside the profiled interval.
+int run_transform(ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, int out_mode,
+                  float* out, bool with_hm, float* hm_rows, int batch_first, int batch_frames, const PfbFold* fold) {
+  const ksa_config& c = e->cfg;
+  if (check_frames(e, iq, fmt, stride, nframes, out, hm_rows)) return 1;
   SpecParams p{};
   p.iq = iq;
   p.frame_stride = stride;
-  p.frame_len = c.full_size;
+  p.frame_len = fold ? c.fft_size : c.full_size;
   p.nframes = nframes;
   const bool raw = c.cumu_mode == KSA_CUMU_RAW;
-  p.nwin = raw ? 1 : c.num_windows;            // RAW keeps the last window only (K:135-136)
+  p.nwin = (raw || fold) ? 1 : c.num_windows;  // RAW keeps the last window only (K:135-136); a folded frame is one window
   p.starts = raw ? e->d_start_last : e->d_starts;
 #if defined(KSA32_TAPS_X4) && !KSA32_TAPS_X4
   p.window = e->d_window;
@@ -646,7 +724,7 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   p.tw_mid = e->d_tw_mid;
   p.tw_last = e->d_tw_last;
   p.scale = (float)c.mag_scale;
-  p.cumu = (raw || c.cumu_mode == KSA_CUMU_AVG || c.cumu_mode == KSA_CUMU_PSD) ? ksa::CUMU_AVG : c.cumu_mode == KSA_CUMU_MAX ? ksa::CUMU_MAX : ksa::CUMU_MIN;
+  p.cumu = (raw || fold || c.cumu_mode == KSA_CUMU_AVG || c.cumu_mode == KSA_CUMU_PSD) ? ksa::CUMU_AVG : c.cumu_mode == KSA_CUMU_MAX ? ksa::CUMU_MAX : ksa::CUMU_MIN;
   p.out_mode = out_mode;
   p.gain = c.gain;
   p.min_amp = c.min_amp;
@@ -673,6 +751,7 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
   if (clk) hipLaunchKernelGGL(ksa::clock_stamp_kernel, dim3(ksa::CLK_WGS), dim3(64), 0, e->stream, clk, 0);
   hipEvent_t ea, eb;
   if (prof_begin(e, &ea, &eb)) return 1;
+  if (fold && launch_pfb(e, *fold)) return 1;
   int rc;
   if (e->path == 2) {
     rc = run_dif16(e, p, fmt, batch_first, batch_frames);
@@ -707,6 +786,28 @@ int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int n
 #endif
   if (prof_end(e, ea, eb)) return 1;
   if (clk) hipLaunchKernelGGL(ksa::clock_stamp_kernel, dim3(ksa::CLK_WGS), dim3(64), 0, e->stream, clk, 1);
+  return 0;
+}
+
+// Spectrum stage of every entry point.  KSA_CUMU_PFB: the batch runs in chunks of pfb_chunk frames -- fold into the engine's
+// scratch, then the transform on that scratch as complex64 frames of N samples at stride N -- and every chunk takes the whole
+// batch's launch plan and ring rows (batch_first / batch_frames), exactly as the slots of a host batch do.
+int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, int out_mode,
+                 float* out, bool with_hm, float* hm_rows, int batch_first = 0, int batch_frames = 0) {
+  if (!fold_pfb(e)) return run_transform(e, iq, fmt, stride, nframes, out_mode, out, with_hm, hm_rows, batch_first, batch_frames, nullptr);
+  const ksa_config& c = e->cfg;
+  if (check_frames(e, iq, fmt, stride, nframes, out, hm_rows)) return 1;
+  if (batch_frames < 1) batch_frames = nframes;
+  const size_t n = (size_t)c.fft_size;
+  for (int f0 = 0; f0 < nframes; f0 += e->pfb_chunk) {
+    PfbFold fold{};
+    fold.iq = static_cast<const unsigned char*>(iq) + (size_t)f0 * (size_t)stride * sample_bytes(fmt);
+    fold.fmt = fmt;
+    fold.stride = stride;
+    fold.nframes = std::min(e->pfb_chunk, nframes - f0);
+    if (run_transform(e, e->d_pfb_y, KSA_FMT_C64, c.fft_size, fold.nframes, out_mode, out + (size_t)f0 * n, with_hm,
+                      hm_rows ? hm_rows + (size_t)f0 * c.hm_width : nullptr, batch_first + f0, batch_frames, &fold)) return 1;
+  }
   return 0;
 }
 
@@ -818,7 +919,10 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   for (int i = 0; i < cfg->num_windows; ++i)
     if (cfg->window_starts[i] < 0 || cfg->window_starts[i] + n > cfg->full_size)
       return fail("window %d start %d runs past the block", i, cfg->window_starts[i]);
-  if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_PSD) return fail("unknown cumu_mode %d", cfg->cumu_mode);
+  if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_PFB) return fail("unknown cumu_mode %d", cfg->cumu_mode);
+  const bool pfb = cfg->cumu_mode == KSA_CUMU_PFB;
+  if (pfb && cfg->num_windows > KSA_PFB_MAX_TAPS)
+    return fail("KSA_CUMU_PFB: num_windows %d outside 1..%d taps", cfg->num_windows, KSA_PFB_MAX_TAPS);
   if (mixed && (cfg->hm_width < 0 || (cfg->hm_width && n % cfg->hm_width)))
     return fail("hm_width %d must divide fft_size %d", cfg->hm_width, n);
   if (!mixed && (cfg->hm_width < 0 || (cfg->hm_width && (n % cfg->hm_width || !is_pow2(cfg->hm_width)))))
@@ -846,10 +950,30 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   int rc = 0;
   auto bail = [&](int r) { ksa_destroy(e); return r; };
 
-  if ((rc = upload(&e->d_starts, cfg->window_starts, (size_t)cfg->num_windows))) return bail(rc);
-  if ((rc = upload(&e->d_start_last, cfg->window_starts + cfg->num_windows - 1, 1))) return bail(rc);
-  if ((rc = upload(&e->d_window, cfg->window, (size_t)n))) return bail(rc);
-  e->win_ones = std::all_of(cfg->window, cfg->window + n, [](float w) { return w == 1.0f; });
+  // What the transform stage plans from and runs on.  KSA_CUMU_PFB: the inner shape -- one window at start 0 with all-ones
+  // taps over a folded frame of N samples; the caller's starts and taps [P][N] belong to the fold (ksa_pfb.hpp).
+  const std::vector<float> pfb_ones(pfb ? (size_t)n : 0, 1.0f);
+  const int32_t pfb_start0 = 0;
+  const int num_windows = pfb ? 1 : cfg->num_windows;
+  const int32_t* const window_starts = pfb ? &pfb_start0 : cfg->window_starts;
+  const float* const window = pfb ? pfb_ones.data() : cfg->window;
+  if (pfb) {
+    if ((rc = upload(&e->d_pfb_starts, cfg->window_starts, (size_t)cfg->num_windows))) return bail(rc);
+    if ((rc = upload(&e->d_pfb_taps, cfg->window, (size_t)cfg->num_windows * n))) return bail(rc);
+    const int p = cfg->num_windows;
+    e->pfb_ring_ok = p == 4 || p == 8 || p == 16;
+    for (int k = 0; k < p; ++k) e->pfb_ring_ok &= (long long)cfg->window_starts[k] == (long long)k * n;
+    // whole frames, a multiple of 4 (even for the pair kernel, 16-byte aligned waterfall row offsets), at least 4
+    const long long chunk = std::max<long long>(4, (long long)KSA_PFB_CHUNK_BYTES / ((long long)n * 8) / 4 * 4);
+    e->pfb_chunk = (int)std::min<long long>(chunk, ((long long)cfg->max_frames + 3) / 4 * 4);
+    hipError_t hp;
+    if ((hp = hipMalloc(reinterpret_cast<void**>(&e->d_pfb_y), (size_t)e->pfb_chunk * n * sizeof(float2))) != hipSuccess)
+      return bail(fail("hipMalloc(%zu) for the folded frames: %s", (size_t)e->pfb_chunk * n * sizeof(float2), hipGetErrorString(hp)));
+  }
+  if ((rc = upload(&e->d_starts, window_starts, (size_t)num_windows))) return bail(rc);
+  if ((rc = upload(&e->d_start_last, window_starts + num_windows - 1, 1))) return bail(rc);
+  if ((rc = upload(&e->d_window, window, (size_t)n))) return bail(rc);
+  e->win_ones = std::all_of(window, window + n, [](float w) { return w == 1.0f; });
 
   if (mixed) {
     e->path = 6;
@@ -943,7 +1067,7 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
       for (int q4 = 0; q4 < 8; ++q4)
         for (int l = 0; l < lth; ++l)
           for (int j = 0; j < 4; ++j)
-            w32[((size_t)q4 * lth + l) * 4 + j] = e->path == 0 ? cfg->window[l + lth * (4 * q4 + j)] : 1.0f;
+            w32[((size_t)q4 * lth + l) * 4 + j] = e->path == 0 ? window[l + lth * (4 * q4 + j)] : 1.0f;
       if ((rc = upload(&e->d_window32, w32.data(), w32.size()))) return bail(rc);
     }
     if (sn == 64 && e->path == 0) {
@@ -959,21 +1083,21 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
     if ((rc = upload(&e->d_tw_mid, mid.data(), mid.size()))) return bail(rc);
     if ((rc = upload(&e->d_tw_last, last.data(), last.size()))) return bail(rc);
     // constant hop of 1/2 or 1/4 of the transform: raw samples are carried over in registers
-    if (e->path == 0 && cfg->num_windows > 1 && n >= 1024) {
-      const int hop = cfg->window_starts[1] - cfg->window_starts[0];
+    if (e->path == 0 && num_windows > 1 && n >= 1024) {
+      const int hop = window_starts[1] - window_starts[0];
       bool same = true;
-      for (int i = 2; i < cfg->num_windows; ++i) same &= cfg->window_starts[i] - cfg->window_starts[i - 1] == hop;
+      for (int i = 2; i < num_windows; ++i) same &= window_starts[i] - window_starts[i - 1] == hop;
       if (same && (hop == n / 2 || hop == n / 4)) e->reuse_m = hop / (n / pt);
     }
     if (exp_env("KSA_NO_REUSE")) e->reuse_m = 0;   // A/B switch of the experiments build
     SpecParams dummy{};
-    dummy.nwin = cfg->num_windows;
+    dummy.nwin = num_windows;
     if ((rc = launch_spec_n<ksa::FMT_C64>(e, dummy, true))) return bail(rc);
     if ((rc = launch_spec_n<ksa::FMT_U8>(e, dummy, true))) return bail(rc);
     if ((rc = launch_spec_n<ksa::FMT_S8>(e, dummy, true))) return bail(rc);
     if ((rc = launch_spec_n<ksa::FMT_S16>(e, dummy, true))) return bail(rc);
     if (e->path == 2) {
-      const int n1 = sn, nw = cfg->num_windows;
+      const int n1 = sn, nw = num_windows;
       // first-stage output twiddles W_N^(n1*e), e = 1,2,3,4,8,12 (float64-generated); w^k2 = w^(k2&3) * w^(k2&12)
       static const int ex[9] = {1, 2, 3, 4, 8, 12, 16, 32, 48};
       const int nrows = e->dif_radix == 16 ? 6 : 9;
@@ -1047,7 +1171,8 @@ void ksa_destroy(ksa_engine* e) {
   void* ptrs[] = {e->d_slot[0], e->d_slot[1], e->d_host_rows, e->d_clk, e->d_gather, e->d_scan_stage, e->d_scan_rows, e->d_scan_halo, e->d_scan_send,
                   e->d_starts, e->d_start_last, e->d_window, e->d_window32, e->d_tw_mid, e->d_tw_last, e->d_adj, e->d_scan_adj,
                   e->d_iq_stage, e->d_frames, e->d_part, e->d_xchg, e->d_state, e->d_scan_state, e->d_scan_hm,
-                  e->d_levels, e->d_parts, e->d_highs, e->d_scan_avg_rows, e->d_dif_tw, e->d_dif_z, e->d_dif_y, e->d_ones, e->d_starts_b};
+                  e->d_levels, e->d_parts, e->d_highs, e->d_scan_avg_rows, e->d_dif_tw, e->d_dif_z, e->d_dif_y, e->d_ones, e->d_starts_b,
+                  e->d_pfb_starts, e->d_pfb_taps, e->d_pfb_y};
   for (void* p : ptrs) if (p) hipFree(p);
   delete e;
 }

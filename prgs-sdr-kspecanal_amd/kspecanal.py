@@ -10,7 +10,9 @@ mode words and aliases (K:816, K:912-921), the defaults (K:41-59), the dict `d` 
 with the same key names, the module-level `sdr_curscan(d)` seam that playback rebinds (K:531, K:543), and the
 arrays handed to matplotlib: d['Fft.Cur'|'Fft.Max'|'Fft.Min'|'Fft.Avg'], the freqs axis, and the
 [128, W] waterfall buffer (K:470-481, K:729).  New keys are additive: `source` (rtlsdr|synth|file:<path>),
-`device`, `iqFormat` (c64|u8|s8|s16), `frameBatch` (zeroSpan blocks per device call, default 1).  What moved to the GPU:
+`device`, `iqFormat` (c64|u8|s8|s16), `frameBatch` (zeroSpan blocks per device call, default 1), `pfbTaps` (P >= 1: the
+polyphase filter bank front end -- P*fftSize samples per spectrum, weighted by a sinc prototype tapered with `window`, folded
+onto fftSize points and transformed once; default 0 = off).  What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
 refreshed once per pass (the whole pass is one device call) instead of once per tuned band, and in zeroSpan with
@@ -59,7 +61,7 @@ _KEYS = {
     "ZEROSPANSAVEFILE": ("zeroSpanSaveFile", str), "ZEROSPANPLAYFILE": ("zeroSpanPlayFile", str),
     # additive keys of this build
     "SOURCE": ("source", str), "DEVICE": ("device", int), "IQFORMAT": ("iqFormat", str.lower),
-    "FRAMEBATCH": ("frameBatch", int),
+    "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int),
 }
 
 
@@ -74,7 +76,7 @@ def defaults():
         "SaveSigLvls": "", "AdjSigLvls": "", "bDataMin": True, "bDataMax": True, "bDataAvg": True, "bDataCur": True,
         "bGrid": True, "bUsePSD": False, "bScanRangeBaseDataIsRaw": False,
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
-        "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "cmd.stop": False,
+        "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "cmd.stop": False,
     }
 
 
@@ -154,7 +156,31 @@ def handle_args(d, argv=None):
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] must be >= 1".format(d["frameBatch"]))
     if d["bUsePSD"] and d["frameBatch"] > 1:
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] needs bUsePSD false: the PSD diagnostic is per block".format(d["frameBatch"]))
+    _handle_pfb(d)
     return d
+
+
+def _handle_pfb(d):
+    """pfbTaps P (additive): the polyphase front end.  fullSize becomes P*fftSize (P segments of fftSize samples per
+    spectrum), `window` names the taper of the prototype; the within-block overlap and fold have nothing left to do."""
+    taps = d["pfbTaps"]
+    if taps < 0 or taps > _engine.PFB_MAX_TAPS:
+        prg_quit(d, "ERROR:handle_args: pfbTaps [{}] must be 0 (off) or 1..{}".format(taps, _engine.PFB_MAX_TAPS))
+    if taps == 0:
+        return
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: pfbTaps [{}] needs bUsePSD false: the PSD diagnostic has no polyphase form".format(taps))
+    if d["curScanCumuMode"] == "PSD":
+        prg_quit(d, "ERROR:handle_args: pfbTaps [{}] cannot be combined with curScanCumuMode PSD".format(taps))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: pfbTaps [{}] is ignored when playing saved spectra".format(taps))
+        d["pfbTaps"] = 0
+        return
+    dflt = defaults()
+    if d["curScanNonOverlap"] != dflt["curScanNonOverlap"] or d["curScanCumuMode"] != dflt["curScanCumuMode"]:
+        print("WARN:handle_args: curScanNonOverlap [{}] and curScanCumuMode [{}] are unused with pfbTaps [{}]".format(
+            d["curScanNonOverlap"], d["curScanCumuMode"], taps))
+    d["fullSize"] = taps * d["fftSize"]
 
 
 def print_info(d):
@@ -171,6 +197,9 @@ def print_info(d):
         d["xRes"], d["bGrid"], d["pltCompress"], d["pltCompressHM"]))
     print("INFO: source [{}], device [{}], iqFormat [{}], frameBatch [{}]".format(d["source"], d["device"], d["iqFormat"],
                                                                                 d["frameBatch"]))
+    if d["pfbTaps"]:
+        print("INFO: pfbTaps [{}]: fullSize[{}] = pfbTaps x fftSize, prototype sinc x window[{}]".format(
+            d["pfbTaps"], d["fullSize"], d["window"]))
 
 
 # ------------------------------------------------------------------------------------------ SDR seam
@@ -273,15 +302,19 @@ def sdr_read(sdr, length, raw=False):
 def get_engine(d, scan_total=0, max_frames=1):
     """One engine per (geometry, mode) -- rebuilt when a GUI toggle or argument changes the key."""
     key = (d["fftSize"], d["fullSize"], d["curScanNonOverlap"], d["curScanCumuMode"], d["window"], d["gain"],
-           d["minAmp4Clip"], d["xRes"], scan_total, d["scanRangeNonOverlap"], max_frames, d["device"])
+           d["minAmp4Clip"], d["xRes"], scan_total, d["scanRangeNonOverlap"], max_frames, d["device"], d.get("pfbTaps", 0))
     if d.get("ksa.key") != key:
         if d.get("ksa.engine") is not None:
             d["ksa.engine"].close()
+        if d.get("pfbTaps", 0):      # the polyphase front end: `window` names the prototype's taper, the fold is the engine's
+            shape = dict(window=d["window"], pfb_taps=d["pfbTaps"])
+        else:
+            shape = dict(window=d["theWin"], cumu_mode=d["curScanCumuMode"])
         d["ksa.engine"] = SpectrumEngine(
-            d["fftSize"], full_size=d["fullSize"], non_overlap=d["curScanNonOverlap"], window=d["theWin"],
-            cumu_mode=d["curScanCumuMode"], gain=d["gain"], min_amp=d["minAmp4Clip"], xres=d["xRes"],
+            d["fftSize"], full_size=d["fullSize"], non_overlap=d["curScanNonOverlap"],
+            gain=d["gain"], min_amp=d["minAmp4Clip"], xres=d["xRes"],
             max_frames=max_frames, device=d["device"], scan_total_entries=scan_total,
-            scan_non_overlap=d["scanRangeNonOverlap"])
+            scan_non_overlap=d["scanRangeNonOverlap"], **shape)
         d["ksa.key"] = key
         if d.get("Fft.Adj") is not None:
             d["ksa.engine"].set_adj(d["Fft.Adj"], scan=bool(scan_total))
