@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -10,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ksa.h"
@@ -20,6 +22,7 @@
 #include "ksa_kernels_pair.hpp"
 #include "ksa_kernels_mr.hpp"
 #include "ksa_pfb.hpp"
+#include "ksa_tables.hpp"
 
 namespace {
 
@@ -83,24 +86,6 @@ constexpr const char* exp_env(const char*) { return nullptr; }
 #ifndef KSA_PFB_CHUNK_BYTES
 #define KSA_PFB_CHUNK_BYTES (256ll << 20)
 #endif
-
-// host mirrors of ksa::Tune<N>::FUSED / FUSED_LAST (the twiddle table layouts depend on them)
-bool tune_fused(int n) {
-#ifdef KSA_FUSED
-  (void)n;
-  return KSA_FUSED;
-#else
-  return n <= 4096;
-#endif
-}
-bool tune_fused_last(int n) {
-#ifdef KSA_FUSED_LAST
-  (void)n;
-  return KSA_FUSED_LAST;
-#else
-  return tune_fused(n);
-#endif
-}
 
 }  // namespace
 
@@ -214,24 +199,121 @@ int plan_of(const ksa_engine* e, const SpecParams& p) { return std::max(p.nframe
 bool fold_psd(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PSD; }
 // KSA_CUMU_PFB engines fold in the time domain (ksa_pfb.hpp) and run the AVG instantiations on one window per folded frame.
 bool fold_pfb(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PFB; }
-size_t sample_bytes(int fmt);   // bytes per IQ sample of a KSA_FMT_* value
+// bytes per IQ sample of a KSA_FMT_* value
+size_t sample_bytes(int fmt) { return fmt == KSA_FMT_C64 ? 8 : fmt == KSA_FMT_S16 ? 4 : 2; }
 
-template <int N, int FMT, int RM, int CM>
-int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only);
+// ---- run-time value -> template constant, each choice written once ---------------------------------------------------------
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <int... V>
+struct Ints {};
+
+// f(int_c<V>{}) for the V of the list that equals `value`; -1 when the list does not hold it (f returns 0 or 1).
+template <class F, int... V>
+int dispatch(int value, Ints<V...>, F&& f) {
+  int rc = -1;
+  (void)((value == V && ((rc = f(int_c<V>{})), true)) || ...);
+  return rc;
+}
+
+// Every sample format, complex64 first: what with_fmt dispatches over and what the configure pass of ksa_create walks.
+// (include/ksa.h and the kernels number the formats alike.)
+using Formats = Ints<ksa::FMT_C64, ksa::FMT_U8, ksa::FMT_S8, ksa::FMT_S16>;
+static_assert(KSA_FMT_C64 == ksa::FMT_C64 && KSA_FMT_U8 == ksa::FMT_U8 && KSA_FMT_S8 == ksa::FMT_S8 && KSA_FMT_S16 == ksa::FMT_S16, "");
+
+template <class F>
+int with_fmt(int fmt, F&& f) {
+  const int rc = dispatch(fmt, Formats{}, f);
+  return rc < 0 ? fail("unknown sample format %d", fmt) : rc;
+}
+template <class F, int... FMT>
+int for_each_fmt(Ints<FMT...>, F&& f) {
+  int rc = 0;
+  (void)((rc = f(int_c<FMT>{})) || ...);
+  return rc;
+}
+
+// Sizes of the 16-point single-workgroup plan (ksa::Plan<N>).
+#ifdef KSA_EXPERIMENTS   // the 16-point plan at 8192 / 16384 is reachable through KSA_PLAN16 only
+using Sizes = Ints<16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384>;
+#else
+using Sizes = Ints<16, 32, 64, 128, 256, 512, 1024, 2048, 4096>;
+#endif
+template <class F>
+int with_size(int sub_n, F&& f) {
+  const int rc = dispatch(sub_n, Sizes{}, f);
+  return rc < 0 ? fail("fft_size %d has no single-workgroup plan", sub_n) : rc;
+}
+
+using Radices = Ints<16, 32, 64>;   // first stage of N > 16384 (ksa_engine::dif_radix)
+
+// Fold mode as a template constant.  A KSA_CUMU_PSD engine: CUMU_PSD.  Otherwise the configure pass visits MAX, MIN, then AVG
+// (AVG last, so that the attributes a launcher records describe the AVG instantiation) and a launch the mode p.cumu names.
+template <class F>
+int with_fold(const ksa_engine* e, const SpecParams& p, bool cfg_only, F&& f) {
+  if (fold_psd(e)) return f(int_c<ksa::CUMU_PSD>{});
+  if (cfg_only) {
+    if (f(int_c<ksa::CUMU_MAX>{}) || f(int_c<ksa::CUMU_MIN>{})) return 1;
+    return f(int_c<ksa::CUMU_AVG>{});
+  }
+  if (p.cumu == ksa::CUMU_AVG) return f(int_c<ksa::CUMU_AVG>{});
+  if (p.cumu == ksa::CUMU_MAX) return f(int_c<ksa::CUMU_MAX>{});
+  return f(int_c<ksa::CUMU_MIN>{});
+}
+constexpr bool fold_avg_or_psd(int cm) { return cm == ksa::CUMU_AVG || cm == ksa::CUMU_PSD; }
+
+// Configure pass of one kernel instantiation: allow it `lds_attr` bytes of dynamic LDS (default: what it is launched with) and
+// report its registers and its workgroups per CU at `threads` x `lds_bytes`.  Whether that goes into the engine is the caller's.
+struct KernelFit {
+  int vgprs = 0, blocks_per_cu = 1;
+};
+template <class K>
+int configure_kernel(K kfn, int threads, int lds_bytes, KernelFit* fit, int lds_attr = -1) {
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr < 0 ? lds_bytes : lds_attr));
+  hipFuncAttributes attr;
+  HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
+  int occ = 0;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, threads, lds_bytes));
+  fit->vgprs = attr.numRegs;
+  fit->blocks_per_cu = std::max(1, occ);
+  return 0;
+}
+
+// Launch of a persistent n-point spectrum kernel over a batch.  Small batches (the per-frame drop-in, one scan pass) where
+// `may_split`: every frame's windows are split over several workgroups so that the GPU is filled, and the partial folds are
+// combined by a second, tiny kernel (pays from N = 1024 up: 84 -> 51 us per block at N=4096, 720 -> 117 us at N=16384; tiny
+// transforms only lose the launches).  `grid_cap` bounds the grid (measurements; INT_MAX otherwise).
+template <class K>
+int launch_split(ksa_engine* e, K kfn, const SpecParams& p, int n, int threads, int lds_bytes, bool may_split, int grid_cap) {
+  const int capacity = e->num_cu * e->blocks_per_cu;
+  SpecParams q = p;
+  const int plan = plan_of(e, p);
+  if (e->d_parts && may_split && !exp_env("KSA_NO_SPLIT") && p.nwin > 1 && plan * 2 <= capacity) {
+    q.parts = std::min(p.nwin, capacity / plan);
+    q.part_out = e->d_parts;
+  }
+  int grid = std::max(1, std::min(q.nframes * std::max(1, q.parts), capacity));
+  grid = std::max(1, std::min(grid, grid_cap));
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), lds_bytes, e->stream, q);
+  if (q.parts > 1) {
+    hipLaunchKernelGGL(ksa::combine_parts_kernel, dim3((n / 4 + 63) / 64, q.nframes), dim3(64), 0, e->stream, q, n);
+    if (q.hm_w > 0)
+      hipLaunchKernelGGL(ksa::rowmax_batch, dim3((q.hm_w + 255) / 256, q.nframes), dim3(256), 0, e->stream, q, n);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
 
 template <int N, int FMT, int RM, int CM>
 int launch_pair_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
   using PP = ksa::PlanPair<N>;
   auto kfn = ksa::spectrum_pair_kernel<N, FMT, RM, CM>;
   if (configure_only) {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS_BYTES));
-    hipFuncAttributes attr;
-    HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
-    int occ = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, ksa::Plan<N>::T, PP::LDS_BYTES));
-    if (FMT == ksa::FMT_C64 && (CM == ksa::CUMU_AVG || CM == ksa::CUMU_PSD)) {
-      e->pair_bpc = std::max(1, occ);
-      e->pair_vgprs = attr.numRegs;
+    KernelFit fit;
+    if (configure_kernel(kfn, ksa::Plan<N>::T, PP::LDS_BYTES, &fit)) return 1;
+    if (FMT == ksa::FMT_C64 && fold_avg_or_psd(CM)) {
+      e->pair_bpc = fit.blocks_per_cu;
+      e->pair_vgprs = fit.vgprs;
       e->pair_lds = PP::LDS_BYTES;
     }
     return 0;
@@ -245,14 +327,27 @@ int launch_pair_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
 
 template <int N, int FMT, int RM>
 int launch_pair(ksa_engine* e, const SpecParams& p, bool cfg_only) {
-  if (fold_psd(e)) return launch_pair_c<N, FMT, RM, ksa::CUMU_PSD>(e, p, cfg_only);
-  if (cfg_only) {
-    if (launch_pair_c<N, FMT, RM, ksa::CUMU_MAX>(e, p, true) || launch_pair_c<N, FMT, RM, ksa::CUMU_MIN>(e, p, true)) return 1;
-    return launch_pair_c<N, FMT, RM, ksa::CUMU_AVG>(e, p, true);
+  return with_fold(e, p, cfg_only, [&](auto cm) { return launch_pair_c<N, FMT, RM, decltype(cm)::value>(e, p, cfg_only); });
+}
+
+template <int N, int FMT, int RM, int CM>
+int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
+  using P = ksa::Plan<N>;
+  auto kfn = ksa::spectrum_kernel<N, FMT, RM, CM>;
+  static const int lds_pad = exp_env("KSA_LDS_PAD_KB") ? atoi(exp_env("KSA_LDS_PAD_KB")) * 1024 : 0;   // occupancy experiments
+  const int lds_bytes = ksa::Tune<N>::LDS_BYTES + lds_pad;
+  if (configure_only) {
+    KernelFit fit;
+    if (configure_kernel(kfn, P::T, lds_bytes, &fit)) return 1;
+    if (FMT == ksa::FMT_C64) {      // (whatever the fold constant: the last one configured stands)
+      e->threads = P::T;
+      e->lds_bytes = ksa::Tune<N>::LDS_BYTES;
+      e->vgprs = fit.vgprs;
+      e->blocks_per_cu = fit.blocks_per_cu;
+    }
+    return 0;
   }
-  if (p.cumu == ksa::CUMU_AVG) return launch_pair_c<N, FMT, RM, ksa::CUMU_AVG>(e, p, false);
-  if (p.cumu == ksa::CUMU_MAX) return launch_pair_c<N, FMT, RM, ksa::CUMU_MAX>(e, p, false);
-  return launch_pair_c<N, FMT, RM, ksa::CUMU_MIN>(e, p, false);
+  return launch_split(e, kfn, p, N, P::T, lds_bytes, N >= 1024, INT_MAX);
 }
 
 template <int N, int FMT, int RM>
@@ -275,60 +370,13 @@ int launch_spec_t(ksa_engine* e, const SpecParams& p, bool configure_only) {
       } else if (plan_of(e, p) >= 2 * e->num_cu * e->pair_bpc) return launch_pair<N, FMT, RM>(e, p, false);
     }
   }
-  if (fold_psd(e)) return launch_spec_c<N, FMT, RM, ksa::CUMU_PSD>(e, p, configure_only);
   // fold mode as a template constant (Tune<N>::fold_const) or as a run-time branch inside the window loop
   if constexpr (ksa::Tune<N>::fold_const(RM)) {
-    if (configure_only) {
-      if (launch_spec_c<N, FMT, RM, ksa::CUMU_MAX>(e, p, true) || launch_spec_c<N, FMT, RM, ksa::CUMU_MIN>(e, p, true)) return 1;
-      return launch_spec_c<N, FMT, RM, ksa::CUMU_AVG>(e, p, true);
-    }
-    if (p.cumu == ksa::CUMU_AVG) return launch_spec_c<N, FMT, RM, ksa::CUMU_AVG>(e, p, false);
-    if (p.cumu == ksa::CUMU_MAX) return launch_spec_c<N, FMT, RM, ksa::CUMU_MAX>(e, p, false);
-    return launch_spec_c<N, FMT, RM, ksa::CUMU_MIN>(e, p, false);
+    return with_fold(e, p, configure_only, [&](auto cm) { return launch_spec_c<N, FMT, RM, decltype(cm)::value>(e, p, configure_only); });
   } else {
+    if (fold_psd(e)) return launch_spec_c<N, FMT, RM, ksa::CUMU_PSD>(e, p, configure_only);
     return launch_spec_c<N, FMT, RM, 0>(e, p, configure_only);
   }
-}
-
-template <int N, int FMT, int RM, int CM>
-int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
-  using P = ksa::Plan<N>;
-  auto kfn = ksa::spectrum_kernel<N, FMT, RM, CM>;
-  static const int lds_pad = exp_env("KSA_LDS_PAD_KB") ? atoi(exp_env("KSA_LDS_PAD_KB")) * 1024 : 0;   // occupancy experiments
-  const int lds_bytes = ksa::Tune<N>::LDS_BYTES + lds_pad;
-  if (configure_only) {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipFuncAttributes attr;
-    HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
-    int occ = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, P::T, lds_bytes));
-    if (FMT == ksa::FMT_C64) {
-      e->threads = P::T;
-      e->lds_bytes = ksa::Tune<N>::LDS_BYTES;
-      e->vgprs = attr.numRegs;
-      e->blocks_per_cu = std::max(1, occ);
-    }
-    return 0;
-  }
-  const int capacity = e->num_cu * e->blocks_per_cu;
-  SpecParams q = p;
-  // small batches (the per-frame drop-in, one scan pass): split every frame's windows over several
-  // workgroups so that the GPU is filled; the partial folds are combined by a second, tiny kernel
-  // (pays from N = 1024 up: 84 -> 51 us per block at N=4096, 720 -> 117 us at N=16384; tiny transforms only lose the launches)
-  const int plan = plan_of(e, p);
-  if (e->d_parts && N >= 1024 && !exp_env("KSA_NO_SPLIT") && p.nwin > 1 && plan * 2 <= capacity) {
-    q.parts = std::min(p.nwin, capacity / plan);
-    q.part_out = e->d_parts;
-  }
-  const int grid = std::max(1, std::min(q.nframes * std::max(1, q.parts), capacity));
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(P::T), lds_bytes, e->stream, q);
-  if (q.parts > 1) {
-    hipLaunchKernelGGL(ksa::combine_parts_kernel, dim3((N / 4 + 63) / 64, q.nframes), dim3(64), 0, e->stream, q, N);
-    if (q.hm_w > 0)
-      hipLaunchKernelGGL(ksa::rowmax_batch, dim3((q.hm_w + 255) / 256, q.nframes), dim3(256), 0, e->stream, q, N);
-  }
-  HIP_OK(hipGetLastError());
-  return 0;
 }
 
 // sample-reuse variants exist where one transform fills the workgroup and the carried samples fit the register
@@ -350,48 +398,23 @@ int launch_spec32_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
   using P = ksa::Plan32<N>;
   auto kfn = ksa::spectrum32_kernel<N, FMT, CM>;
   if (configure_only) {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, P::LDS_BYTES));
-    hipFuncAttributes attr;
-    HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
-    int occ = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, P::T, P::LDS_BYTES));
-    if (FMT == ksa::FMT_C64 && (CM == ksa::CUMU_AVG || CM == ksa::CUMU_PSD)) {
+    KernelFit fit;
+    if (configure_kernel(kfn, P::T, P::LDS_BYTES, &fit)) return 1;
+    if (FMT == ksa::FMT_C64 && fold_avg_or_psd(CM)) {
       e->threads = P::T;
       e->lds_bytes = P::LDS_BYTES;
-      e->vgprs = attr.numRegs;
-      e->blocks_per_cu = std::max(1, occ);
+      e->vgprs = fit.vgprs;
+      e->blocks_per_cu = fit.blocks_per_cu;
     }
     return 0;
   }
-  const int capacity = e->num_cu * e->blocks_per_cu;
-  SpecParams q = p;
-  const int plan = plan_of(e, p);
-  if (e->d_parts && !exp_env("KSA_NO_SPLIT") && p.nwin > 1 && plan * 2 <= capacity) {   // window-split (latency) mode
-    q.parts = std::min(p.nwin, capacity / plan);
-    q.part_out = e->d_parts;
-  }
-  int grid = std::max(1, std::min(q.nframes * std::max(1, q.parts), capacity));
-  if (const char* g = exp_env("KSA_GRID")) grid = std::max(1, std::min(grid, atoi(g)));   // measurement: fewer persistent workgroups
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(P::T), P::LDS_BYTES, e->stream, q);
-  if (q.parts > 1) {
-    hipLaunchKernelGGL(ksa::combine_parts_kernel, dim3((N / 4 + 63) / 64, q.nframes), dim3(64), 0, e->stream, q, N);
-    if (q.hm_w > 0)
-      hipLaunchKernelGGL(ksa::rowmax_batch, dim3((q.hm_w + 255) / 256, q.nframes), dim3(256), 0, e->stream, q, N);
-  }
-  HIP_OK(hipGetLastError());
-  return 0;
+  const char* g = exp_env("KSA_GRID");   // measurement: fewer persistent workgroups
+  return launch_split(e, kfn, p, N, P::T, P::LDS_BYTES, true, g ? atoi(g) : INT_MAX);
 }
 
 template <int N, int FMT>
 int launch_spec32(ksa_engine* e, const SpecParams& p, bool cfg_only) {
-  if (fold_psd(e)) return launch_spec32_c<N, FMT, ksa::CUMU_PSD>(e, p, cfg_only);
-  if (cfg_only) {
-    if (launch_spec32_c<N, FMT, ksa::CUMU_MAX>(e, p, true) || launch_spec32_c<N, FMT, ksa::CUMU_MIN>(e, p, true)) return 1;
-    return launch_spec32_c<N, FMT, ksa::CUMU_AVG>(e, p, true);
-  }
-  if (p.cumu == ksa::CUMU_AVG) return launch_spec32_c<N, FMT, ksa::CUMU_AVG>(e, p, false);
-  if (p.cumu == ksa::CUMU_MAX) return launch_spec32_c<N, FMT, ksa::CUMU_MAX>(e, p, false);
-  return launch_spec32_c<N, FMT, ksa::CUMU_MIN>(e, p, false);
+  return with_fold(e, p, cfg_only, [&](auto cm) { return launch_spec32_c<N, FMT, decltype(cm)::value>(e, p, cfg_only); });
 }
 
 // N = 64, complex64 input: 8 x 8 with adjacent samples per lane (ksa_kernels64.hpp)
@@ -399,14 +422,11 @@ template <int CM, bool W1>
 int launch_spec64_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
   auto kfn = ksa::spectrum64_kernel<ksa::FMT_C64, CM, W1>;
   if (configure_only) {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, ksa::Plan64::LDS_BYTES));
-    int occ = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, ksa::Plan64::T, ksa::Plan64::LDS_BYTES));
-    if (CM == ksa::CUMU_AVG || CM == ksa::CUMU_PSD) {
-      hipFuncAttributes attr;
-      HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
-      e->k64_bpc = std::max(1, occ);
-      e->k64_vgprs = attr.numRegs;
+    KernelFit fit;
+    if (configure_kernel(kfn, ksa::Plan64::T, ksa::Plan64::LDS_BYTES, &fit)) return 1;
+    if (fold_avg_or_psd(CM)) {
+      e->k64_bpc = fit.blocks_per_cu;
+      e->k64_vgprs = fit.vgprs;
     }
     return 0;
   }
@@ -416,73 +436,48 @@ int launch_spec64_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
   return 0;
 }
 
-template <bool W1>
-int launch_spec64_w(ksa_engine* e, const SpecParams& p, bool cfg_only) {
-  if (fold_psd(e)) return launch_spec64_c<ksa::CUMU_PSD, W1>(e, p, cfg_only);
-  if (cfg_only) {
-    if (launch_spec64_c<ksa::CUMU_MAX, W1>(e, p, true) || launch_spec64_c<ksa::CUMU_MIN, W1>(e, p, true)) return 1;
-    return launch_spec64_c<ksa::CUMU_AVG, W1>(e, p, true);
-  }
-  if (p.cumu == ksa::CUMU_AVG) return launch_spec64_c<ksa::CUMU_AVG, W1>(e, p, false);
-  if (p.cumu == ksa::CUMU_MAX) return launch_spec64_c<ksa::CUMU_MAX, W1>(e, p, false);
-  return launch_spec64_c<ksa::CUMU_MIN, W1>(e, p, false);
-}
 int launch_spec64(ksa_engine* e, const SpecParams& p, bool cfg_only) {
   // (p.window is the engine's own table here: the first-stage paths, which hand this stage a table of ones, start at N = 32768)
-  return e->win_ones && !exp_env("KSA_NO_W1") ? launch_spec64_w<true>(e, p, cfg_only) : launch_spec64_w<false>(e, p, cfg_only);
+  const bool w1 = e->win_ones && !exp_env("KSA_NO_W1");
+  return with_fold(e, p, cfg_only, [&](auto cm) {
+    constexpr int CM = decltype(cm)::value;
+    return w1 ? launch_spec64_c<CM, true>(e, p, cfg_only) : launch_spec64_c<CM, false>(e, p, cfg_only);
+  });
 }
 
 template <int FMT>
 int launch_spec_n(ksa_engine* e, const SpecParams& p, bool cfg_only) {
   const int rm = p.nwin > 1 ? e->reuse_m : 0;   // RAW mode transforms a single window: nothing to reuse
   if (e->plan32) return e->sub_n == 8192 ? launch_spec32<8192, FMT>(e, p, cfg_only) : launch_spec32<16384, FMT>(e, p, cfg_only);
-  switch (e->sub_n) {
-    case 16: return launch_spec_rm<16, FMT>(e, p, cfg_only, rm);
-    case 32: return launch_spec_rm<32, FMT>(e, p, cfg_only, rm);
-    case 64:
-      if constexpr (FMT == ksa::FMT_C64) {
-        if (e->k64_ok) {
-          if (cfg_only) { if (launch_spec64(e, p, true)) return 1; }     // (then the general kernel's attributes too: uint8 input runs it)
-          else if (!exp_env("KSA_NO_K64")) return launch_spec64(e, p, false);
-        }
+  return with_size(e->sub_n, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    if constexpr (N == 64 && FMT == ksa::FMT_C64) {
+      if (e->k64_ok) {
+        if (cfg_only) { if (launch_spec64(e, p, true)) return 1; }     // (then the general kernel's attributes too: uint8 input runs it)
+        else if (!exp_env("KSA_NO_K64")) return launch_spec64(e, p, false);
       }
-      return launch_spec_rm<64, FMT>(e, p, cfg_only, rm);
-    case 128: return launch_spec_rm<128, FMT>(e, p, cfg_only, rm);
-    case 256: return launch_spec_rm<256, FMT>(e, p, cfg_only, rm);
-    case 512: return launch_spec_rm<512, FMT>(e, p, cfg_only, rm);
-    case 1024: return launch_spec_rm<1024, FMT>(e, p, cfg_only, rm);
-    case 2048: return launch_spec_rm<2048, FMT>(e, p, cfg_only, rm);
-    case 4096: return launch_spec_rm<4096, FMT>(e, p, cfg_only, rm);
-#ifdef KSA_EXPERIMENTS   // the 16-point plan at these sizes is reachable through KSA_PLAN16 only
-    case 8192: return launch_spec_rm<8192, FMT>(e, p, cfg_only, rm);
-    case 16384: return launch_spec_rm<16384, FMT>(e, p, cfg_only, rm);
-#endif
-    default: return fail("fft_size %d has no single-workgroup plan", e->sub_n);
-  }
+    }
+    return launch_spec_rm<N, FMT>(e, p, cfg_only, rm);
+  });
 }
 
 // fft_size 2^a * 3^b * 5^c (path 6): the mixed-radix kernel, one frame per workgroup at the plan's thread count.  It has no
 // window split (p.parts): a one-frame batch runs on one workgroup.
-template <int FMT, bool PSD = false>
+template <int FMT>
 int launch_mr(ksa_engine* e, const SpecParams& p, bool configure_only) {
-  if constexpr (!PSD) {
-    if (fold_psd(e)) return launch_mr<FMT, true>(e, p, configure_only);
-  }
+  const bool psd = fold_psd(e);
   void (*kfn)(const SpecParams, const ksa::MrPlan);
-  if constexpr (FMT == ksa::FMT_S8 || FMT == ksa::FMT_S16) kfn = ksa::mixed_radix_fixed_kernel<FMT, PSD ? ksa::CUMU_PSD : 0>;
-  else kfn = PSD ? ksa::mixed_radix_psd_kernel<FMT> : ksa::mixed_radix_kernel<FMT>;
+  if constexpr (FMT == ksa::FMT_S8 || FMT == ksa::FMT_S16) kfn = psd ? ksa::mixed_radix_fixed_kernel<FMT, ksa::CUMU_PSD> : ksa::mixed_radix_fixed_kernel<FMT, 0>;
+  else kfn = psd ? ksa::mixed_radix_psd_kernel<FMT> : ksa::mixed_radix_kernel<FMT>;
   const int lds_bytes = e->mr.n * (int)sizeof(float2);
   if (configure_only) {
     // (one kernel serves every N of the path: its attribute is set to the largest transform, not to this engine's)
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * (int)sizeof(float2)));
-    hipFuncAttributes attr;
-    HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kfn)));
-    int occ = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, e->threads, lds_bytes));
+    KernelFit fit;
+    if (configure_kernel(kfn, e->threads, lds_bytes, &fit, 16384 * (int)sizeof(float2))) return 1;
     if (FMT == ksa::FMT_C64) {
       e->lds_bytes = lds_bytes;
-      e->vgprs = attr.numRegs;
-      e->blocks_per_cu = std::max(1, occ);
+      e->vgprs = fit.vgprs;
+      e->blocks_per_cu = fit.blocks_per_cu;
     }
     return 0;
   }
@@ -492,55 +487,26 @@ int launch_mr(ksa_engine* e, const SpecParams& p, bool configure_only) {
   return 0;
 }
 
-// Plan of path 6: radix-5 passes, radix-3 passes, radix-4 passes, one radix-2 pass if the power of two is odd, and the radix-4
-// pass that every plan ends with (N % 4 == 0).  Twiddles in double, stored as float: pass s with ns = product of the radices
-// before it holds [R-1][ns] = W_(ns*R)^(r*k), r = 1..R-1, k < ns.  Threads: the fewest (a multiple of 64) that keep every
-// pass at ceil(N / (R*T)) <= MrNb<R> butterflies per thread.
-int plan_mr(int n, ksa::MrPlan* plan, int* threads, std::vector<float2>* tw) {
-  int m = n / 4, a = 0, b = 0, c = 0;
-  while (m % 2 == 0) { m /= 2; ++a; }
-  while (m % 3 == 0) { m /= 3; ++b; }
-  while (m % 5 == 0) { m /= 5; ++c; }
-  if (m != 1) return fail("fft_size %d is not 4 * 2^a * 3^b * 5^c", n);
-  std::vector<int> r;
-  r.insert(r.end(), c, 5);
-  r.insert(r.end(), b, 3);
-  r.insert(r.end(), a / 2, 4);
-  if (a % 2) r.push_back(2);
-  r.push_back(4);
-  if ((int)r.size() > ksa::MR_MAX_PASSES) return fail("fft_size %d needs %zu passes (> %d)", n, r.size(), ksa::MR_MAX_PASSES);
-  *plan = ksa::MrPlan{};
-  plan->n = n;
-  plan->npass = (int)r.size();
-  tw->clear();
-  int ns = 1;
-  for (int s = 0; s < plan->npass; ++s) {
-    const int R = r[s];
-    plan->radix[s] = R;
-    plan->tw_off[s] = (int)tw->size();
-    if (s > 0)
-      for (int q = 1; q < R; ++q)
-        for (int k = 0; k < ns; ++k) {
-          const double ang = -2.0 * M_PI * (double)q * (double)k / ((double)ns * R);
-          tw->push_back(make_float2((float)std::cos(ang), (float)std::sin(ang)));
-        }
-    ns *= R;
-  }
-  auto nb = [](int R) { return R == 2 ? 8 : R == 3 ? 6 : 4; };    // ksa::MrNb<R>
-  for (int t = 64; t <= ksa::MR_MAX_THREADS; t += 64) {
-    bool fits = true;
-    for (int R : r) fits &= (n / R + t - 1) / t <= nb(R);
-    if (fits) { *threads = t; return 0; }
-  }
-  return fail("fft_size %d needs more than %d threads", n, ksa::MR_MAX_THREADS);
+// Configure pass of an engine: every kernel a later call of any sample format can launch.
+int configure_kernels(ksa_engine* e, int num_windows) {
+  SpecParams dummy{};
+  dummy.nwin = num_windows;
+  return for_each_fmt(Formats{}, [&](auto f) {
+    constexpr int FMT = decltype(f)::value;
+    return e->path == 6 ? launch_mr<FMT>(e, dummy, true) : launch_spec_n<FMT>(e, dummy, true);
+  });
 }
 
-// One fold launch of a KSA_CUMU_PFB engine: `nframes` frames of the caller's samples -> d_pfb_y[nframes][N].
-struct PfbFold {
-  const void* iq;       // first frame of the chunk
+// The samples a spectrum-stage call is handed: `nframes` frames from `iq`, `stride` samples apart.  They are frames
+// [batch_first, batch_first + nframes) of a batch of batch_frames (0: nframes; run_spectrum resolves it) whose launch plan,
+// ring rows and ring window the call takes: slot by slot (a host batch) or chunk by chunk it writes what one call over the
+// batch writes.
+struct Frames {
+  const void* iq;
   int fmt;
-  long long stride;     // samples between frames
-  int nframes;          // <= pfb_chunk
+  long long stride;
+  int nframes;
+  int batch_first = 0, batch_frames = 0;
 };
 
 template <int FMT>
@@ -565,7 +531,8 @@ int launch_pfb_fmt(ksa_engine* e, const ksa::PfbParams& a, bool ring) {
   return 0;
 }
 
-int launch_pfb(ksa_engine* e, const PfbFold& f) {
+// One fold launch of a KSA_CUMU_PFB engine: the caller's frames `f` (at most pfb_chunk) -> d_pfb_y[nframes][N].
+int launch_pfb(ksa_engine* e, const Frames& f) {
   const ksa_config& c = e->cfg;
   ksa::PfbParams a{};
   a.iq = f.iq;
@@ -583,8 +550,7 @@ int launch_pfb(ksa_engine* e, const PfbFold& f) {
   // bytes up it won (complex64 P >= 4, 2-byte samples P >= 8), below that the generic kernel's re-reads hit in cache and it lost.
   // (KSA_PFB_NO_RING: A/B switch of the experiments build.)
   const bool ring = e->pfb_ring_ok && f.stride == c.fft_size && ksa::pfb_ring_pays(f.fmt, c.num_windows) && !exp_env("KSA_PFB_NO_RING");
-  return f.fmt == KSA_FMT_C64 ? launch_pfb_fmt<ksa::FMT_C64>(e, a, ring) : f.fmt == KSA_FMT_S8 ? launch_pfb_fmt<ksa::FMT_S8>(e, a, ring)
-         : f.fmt == KSA_FMT_S16 ? launch_pfb_fmt<ksa::FMT_S16>(e, a, ring) : launch_pfb_fmt<ksa::FMT_U8>(e, a, ring);
+  return with_fmt(f.fmt, [&](auto fmt) { return launch_pfb_fmt<decltype(fmt)::value>(e, a, ring); });
 }
 
 int prof_begin(ksa_engine* e, hipEvent_t* a, hipEvent_t* b) {
@@ -626,23 +592,17 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int 
     a.u8_inv_scale = p.u8_inv_scale;
     a.z = e->d_dif_z;
     const int R = e->dif_radix;
-    if (R == 16) {
-      const dim3 ga(n1 / 512, nwin, cf);     // two adjacent n1 per thread
-      if (fmt == KSA_FMT_C64) hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_C64>, ga, dim3(256), 0, e->stream, a);
-      else if (fmt == KSA_FMT_S8) hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_S8>, ga, dim3(256), 0, e->stream, a);
-      else if (fmt == KSA_FMT_S16) hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_S16>, ga, dim3(256), 0, e->stream, a);
-      else hipLaunchKernelGGL(ksa::dif16_kernel<ksa::FMT_U8>, ga, dim3(256), 0, e->stream, a);
-    } else {
-      const dim3 ga(n1 / 256, nwin, cf);     // one n1 per thread, 32 or 64 samples in registers
-      if (R == 32 && fmt == KSA_FMT_C64) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_C64, 32>), ga, dim3(256), 0, e->stream, a);
-      else if (R == 32 && fmt == KSA_FMT_S8) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S8, 32>), ga, dim3(256), 0, e->stream, a);
-      else if (R == 32 && fmt == KSA_FMT_S16) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S16, 32>), ga, dim3(256), 0, e->stream, a);
-      else if (R == 32) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_U8, 32>), ga, dim3(256), 0, e->stream, a);
-      else if (fmt == KSA_FMT_C64) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_C64, 64>), ga, dim3(256), 0, e->stream, a);
-      else if (fmt == KSA_FMT_S8) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S8, 64>), ga, dim3(256), 0, e->stream, a);
-      else if (fmt == KSA_FMT_S16) hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_S16, 64>), ga, dim3(256), 0, e->stream, a);
-      else hipLaunchKernelGGL((ksa::dif_wide_kernel<ksa::FMT_U8, 64>), ga, dim3(256), 0, e->stream, a);
-    }
+    if (with_fmt(fmt, [&](auto f) {
+          constexpr int FMT = decltype(f)::value;
+          return dispatch(R, Radices{}, [&](auto radix) {
+            constexpr int RX = decltype(radix)::value;
+            if constexpr (RX == 16)     // two adjacent n1 per thread
+              hipLaunchKernelGGL(ksa::dif16_kernel<FMT>, dim3(n1 / 512, nwin, cf), dim3(256), 0, e->stream, a);
+            else                        // one n1 per thread, 32 or 64 samples in registers
+              hipLaunchKernelGGL((ksa::dif_wide_kernel<FMT, RX>), dim3(n1 / 256, nwin, cf), dim3(256), 0, e->stream, a);
+            return 0;
+          });
+        })) return 1;
     SpecParams b{};
     b.iq = e->d_dif_z;
     b.frame_stride = (long long)nwin * n1;
@@ -675,10 +635,10 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int 
     c.hm_ring = p.hm_ring;
     c.hm_index0 = p.hm_index0;
     c.hm_first = p.hm_first;
-    const dim3 gf(n1 / (1024 / R), cf);
-    if (R == 16) hipLaunchKernelGGL(ksa::dif16_finish_kernel<16>, gf, dim3(256), 0, e->stream, c);
-    else if (R == 32) hipLaunchKernelGGL(ksa::dif16_finish_kernel<32>, gf, dim3(256), 0, e->stream, c);
-    else hipLaunchKernelGGL(ksa::dif16_finish_kernel<64>, gf, dim3(256), 0, e->stream, c);
+    dispatch(R, Radices{}, [&](auto radix) {
+      hipLaunchKernelGGL(ksa::dif16_finish_kernel<decltype(radix)::value>, dim3(n1 / (1024 / R), cf), dim3(256), 0, e->stream, c);
+      return 0;
+    });
   }
   if (p.hm_w > 0 && n / p.hm_w > 1024)      // cells wider than the finish kernel's tile
     hipLaunchKernelGGL(ksa::rowmax_batch, dim3((p.hm_w + 255) / 256, p.nframes), dim3(256), 0, e->stream, p, n);
@@ -686,33 +646,30 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int 
   return 0;
 }
 
-// Spectrum stage for a batch: the single-workgroup LDS FFT, behind a radix-16 / 32 / 64 first stage for N > 16384.
-// The call transforms frames [batch_first, batch_first + nframes) of a batch of batch_frames (0: nframes) and takes the
-// whole batch's launch plan, ring rows and ring window: slot by slot it writes what one call over the batch writes.
 // What every spectrum-stage call checks on the samples it is handed (the caller's, or a chunk of folded frames).
-int check_frames(const ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, const float* out, const float* hm_rows) {
+int check_frames(const ksa_engine* e, const Frames& f, const float* out, const float* hm_rows) {
   const ksa_config& c = e->cfg;
-  if (fmt != KSA_FMT_C64 && fmt != KSA_FMT_U8 && fmt != KSA_FMT_S8 && fmt != KSA_FMT_S16) return fail("unknown sample format %d", fmt);
-  if (nframes < 1 || nframes > c.max_frames) return fail("nframes %d outside 1..max_frames(%d)", nframes, c.max_frames);
-  if (stride < 0) return fail("negative frame_stride");
-  if (stride > (1ll << 27)) return fail("frame_stride %lld exceeds 2^27 samples", stride);
+  if (f.fmt != KSA_FMT_C64 && f.fmt != KSA_FMT_U8 && f.fmt != KSA_FMT_S8 && f.fmt != KSA_FMT_S16) return fail("unknown sample format %d", f.fmt);
+  if (f.nframes < 1 || f.nframes > c.max_frames) return fail("nframes %d outside 1..max_frames(%d)", f.nframes, c.max_frames);
+  if (f.stride < 0) return fail("negative frame_stride");
+  if (f.stride > (1ll << 27)) return fail("frame_stride %lld exceeds 2^27 samples", f.stride);
   // the output stage stores float4 runs; IQ loads are per-sample but frames should start on sample bounds
   if ((reinterpret_cast<uintptr_t>(out) & 15) || (hm_rows && (reinterpret_cast<uintptr_t>(hm_rows) & 15)))
     return fail("device output buffers must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(iq) & (sample_bytes(fmt) - 1)) return fail("IQ buffer is not sample aligned");
+  if (reinterpret_cast<uintptr_t>(f.iq) & (sample_bytes(f.fmt) - 1)) return fail("IQ buffer is not sample aligned");
   return 0;
 }
 
-// `fold` (KSA_CUMU_PFB): the fold launch that fills `iq` for these frames, enqueued inside the profiled interval.
-int run_transform(ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, int out_mode,
-                  float* out, bool with_hm, float* hm_rows, int batch_first, int batch_frames, const PfbFold* fold) {
+// Spectrum stage for a batch: the single-workgroup LDS FFT, behind a radix-16 / 32 / 64 first stage for N > 16384.
+// `fold` (KSA_CUMU_PFB): the fold launch that fills f.iq for these frames, enqueued inside the profiled interval.
+int run_transform(ksa_engine* e, const Frames& f, int out_mode, float* out, bool with_hm, float* hm_rows, const Frames* fold) {
   const ksa_config& c = e->cfg;
-  if (check_frames(e, iq, fmt, stride, nframes, out, hm_rows)) return 1;
+  if (check_frames(e, f, out, hm_rows)) return 1;
   SpecParams p{};
-  p.iq = iq;
-  p.frame_stride = stride;
+  p.iq = f.iq;
+  p.frame_stride = f.stride;
   p.frame_len = fold ? c.fft_size : c.full_size;
-  p.nframes = nframes;
+  p.nframes = f.nframes;
   const bool raw = c.cumu_mode == KSA_CUMU_RAW;
   p.nwin = (raw || fold) ? 1 : c.num_windows;  // RAW keeps the last window only (K:135-136); a folded frame is one window
   p.starts = raw ? e->d_start_last : e->d_starts;
@@ -735,10 +692,9 @@ int run_transform(ksa_engine* e, const void* iq, int fmt, long long stride, int 
   p.adj = with_hm ? e->d_adj : nullptr;
   p.hm_rows = with_hm ? hm_rows : nullptr;
   p.hm_ring = with_hm ? e->d_hm : nullptr;
-  if (batch_frames < 1) batch_frames = nframes;
-  p.hm_index0 = (e->hm_index + batch_first) % KSA_HM_ROWS;
-  p.hm_first = std::max(0, batch_frames - KSA_HM_ROWS - batch_first);
-  e->plan_frames = batch_frames;
+  p.hm_index0 = (e->hm_index + f.batch_first) % KSA_HM_ROWS;
+  p.hm_first = std::max(0, f.batch_frames - KSA_HM_ROWS - f.batch_first);
+  e->plan_frames = f.batch_frames;
 #ifdef KSA_STAMPS
   static unsigned long long* dbg = nullptr;   // diagnostic build: 4096 blocks x 16 waves x 12 segments
   const size_t dbg_n = 4096 * 16 * 12;
@@ -753,15 +709,9 @@ int run_transform(ksa_engine* e, const void* iq, int fmt, long long stride, int 
   if (prof_begin(e, &ea, &eb)) return 1;
   if (fold && launch_pfb(e, *fold)) return 1;
   int rc;
-  if (e->path == 2) {
-    rc = run_dif16(e, p, fmt, batch_first, batch_frames);
-  } else if (e->path == 6) {
-    rc = fmt == KSA_FMT_C64 ? launch_mr<ksa::FMT_C64>(e, p, false) : fmt == KSA_FMT_S8 ? launch_mr<ksa::FMT_S8>(e, p, false)
-         : fmt == KSA_FMT_S16 ? launch_mr<ksa::FMT_S16>(e, p, false) : launch_mr<ksa::FMT_U8>(e, p, false);
-  } else {
-    rc = fmt == KSA_FMT_C64 ? launch_spec_n<ksa::FMT_C64>(e, p, false) : fmt == KSA_FMT_S8 ? launch_spec_n<ksa::FMT_S8>(e, p, false)
-         : fmt == KSA_FMT_S16 ? launch_spec_n<ksa::FMT_S16>(e, p, false) : launch_spec_n<ksa::FMT_U8>(e, p, false);
-  }
+  if (e->path == 2) rc = run_dif16(e, p, f.fmt, f.batch_first, f.batch_frames);
+  else if (e->path == 6) rc = with_fmt(f.fmt, [&](auto fmt) { return launch_mr<decltype(fmt)::value>(e, p, false); });
+  else rc = with_fmt(f.fmt, [&](auto fmt) { return launch_spec_n<decltype(fmt)::value>(e, p, false); });
   e->plan_frames = 0;
   if (rc) return rc;
 #ifdef KSA_STAMPS
@@ -776,11 +726,11 @@ int run_transform(ksa_engine* e, const void* iq, int fmt, long long stride, int 
       ++waves;
       for (int i = 0; i < 12; ++i) sum[i] += (double)h[w * 12 + i];
     }
-    if (FILE* f = fopen(path, "a")) {
-      fprintf(f, "waves %lld nframes %d nwin %d :", waves, nframes, p.nwin);
-      for (int i = 0; i < 12; ++i) fprintf(f, " %.0f", waves ? sum[i] / waves : 0.0);
-      fprintf(f, "\n");
-      fclose(f);
+    if (FILE* fp = fopen(path, "a")) {
+      fprintf(fp, "waves %lld nframes %d nwin %d :", waves, f.nframes, p.nwin);
+      for (int i = 0; i < 12; ++i) fprintf(fp, " %.0f", waves ? sum[i] / waves : 0.0);
+      fprintf(fp, "\n");
+      fclose(fp);
     }
   }
 #endif
@@ -792,21 +742,17 @@ int run_transform(ksa_engine* e, const void* iq, int fmt, long long stride, int 
 // Spectrum stage of every entry point.  KSA_CUMU_PFB: the batch runs in chunks of pfb_chunk frames -- fold into the engine's
 // scratch, then the transform on that scratch as complex64 frames of N samples at stride N -- and every chunk takes the whole
 // batch's launch plan and ring rows (batch_first / batch_frames), exactly as the slots of a host batch do.
-int run_spectrum(ksa_engine* e, const void* iq, int fmt, long long stride, int nframes, int out_mode,
-                 float* out, bool with_hm, float* hm_rows, int batch_first = 0, int batch_frames = 0) {
-  if (!fold_pfb(e)) return run_transform(e, iq, fmt, stride, nframes, out_mode, out, with_hm, hm_rows, batch_first, batch_frames, nullptr);
+int run_spectrum(ksa_engine* e, Frames f, int out_mode, float* out, bool with_hm, float* hm_rows) {
+  if (f.batch_frames < 1) f.batch_frames = f.nframes;
+  if (!fold_pfb(e)) return run_transform(e, f, out_mode, out, with_hm, hm_rows, nullptr);
   const ksa_config& c = e->cfg;
-  if (check_frames(e, iq, fmt, stride, nframes, out, hm_rows)) return 1;
-  if (batch_frames < 1) batch_frames = nframes;
+  if (check_frames(e, f, out, hm_rows)) return 1;
   const size_t n = (size_t)c.fft_size;
-  for (int f0 = 0; f0 < nframes; f0 += e->pfb_chunk) {
-    PfbFold fold{};
-    fold.iq = static_cast<const unsigned char*>(iq) + (size_t)f0 * (size_t)stride * sample_bytes(fmt);
-    fold.fmt = fmt;
-    fold.stride = stride;
-    fold.nframes = std::min(e->pfb_chunk, nframes - f0);
-    if (run_transform(e, e->d_pfb_y, KSA_FMT_C64, c.fft_size, fold.nframes, out_mode, out + (size_t)f0 * n, with_hm,
-                      hm_rows ? hm_rows + (size_t)f0 * c.hm_width : nullptr, batch_first + f0, batch_frames, &fold)) return 1;
+  for (int f0 = 0; f0 < f.nframes; f0 += e->pfb_chunk) {
+    const int nf = std::min(e->pfb_chunk, f.nframes - f0);
+    const Frames fold{static_cast<const unsigned char*>(f.iq) + (size_t)f0 * (size_t)f.stride * sample_bytes(f.fmt), f.fmt, f.stride, nf};
+    const Frames folded{e->d_pfb_y, KSA_FMT_C64, c.fft_size, nf, f.batch_first + f0, f.batch_frames};
+    if (run_transform(e, folded, out_mode, out + (size_t)f0 * n, with_hm, hm_rows ? hm_rows + (size_t)f0 * c.hm_width : nullptr, &fold)) return 1;
   }
   return 0;
 }
@@ -884,8 +830,6 @@ int scan_reset(ksa_engine* e) {
   return 0;
 }
 
-size_t sample_bytes(int fmt) { return fmt == KSA_FMT_C64 ? 8 : fmt == KSA_FMT_S16 ? 4 : 2; }
-
 // Grow-only device scratch of an engine (on its device, which the caller has made current).
 template <typename T>
 int ensure(T** ptr, size_t* cap, size_t count) {
@@ -898,17 +842,9 @@ int ensure(T** ptr, size_t* cap, size_t count) {
   return 0;
 }
 
-
-}  // namespace
-
-extern "C" {
-
-int ksa_abi_version(void) { return KSA_ABI_VERSION; }
-const char* ksa_last_error(void) { return g_err.c_str(); }
-
-int ksa_create(const ksa_config* cfg, ksa_engine** out) {
-  if (!cfg || !out) return fail("null argument");
-  *out = nullptr;
+// ---- ksa_create, step by step ------------------------------------------------------------------------------------------------
+// 1. the checks that need no device
+int validate_config(const ksa_config* cfg) {
   if (cfg->abi_version != KSA_ABI_VERSION) return fail("ABI version %d, library is %d", cfg->abi_version, KSA_ABI_VERSION);
   const int n = cfg->fft_size;
   const bool mixed = is_mixed_radix(n);
@@ -920,8 +856,7 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
     if (cfg->window_starts[i] < 0 || cfg->window_starts[i] + n > cfg->full_size)
       return fail("window %d start %d runs past the block", i, cfg->window_starts[i]);
   if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_PFB) return fail("unknown cumu_mode %d", cfg->cumu_mode);
-  const bool pfb = cfg->cumu_mode == KSA_CUMU_PFB;
-  if (pfb && cfg->num_windows > KSA_PFB_MAX_TAPS)
+  if (cfg->cumu_mode == KSA_CUMU_PFB && cfg->num_windows > KSA_PFB_MAX_TAPS)
     return fail("KSA_CUMU_PFB: num_windows %d outside 1..%d taps", cfg->num_windows, KSA_PFB_MAX_TAPS);
   if (mixed && (cfg->hm_width < 0 || (cfg->hm_width && n % cfg->hm_width)))
     return fail("hm_width %d must divide fft_size %d", cfg->hm_width, n);
@@ -934,6 +869,160 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
     if (cfg->scan_hm_width < 1 || cfg->scan_total_entries % cfg->scan_hm_width)
       return fail("scan_hm_width %d must divide scan_total_entries %d", cfg->scan_hm_width, cfg->scan_total_entries);
   }
+  return 0;
+}
+
+// What the transform stage plans from and runs on: the caller's windows or, on a KSA_CUMU_PFB engine, the inner shape -- one
+// window at start 0 with all-ones taps over a folded frame of N samples (the caller's starts and taps [P][N] belong to the fold).
+struct WindowShape {
+  int num_windows;
+  const int32_t* starts;
+  const float* taps;
+};
+
+// 2. path and plan: which kernels serve the engine (no HIP call)
+void choose_plan(ksa_engine* e, const ksa_config* cfg, const WindowShape& w) {
+  const int n = cfg->fft_size;
+  e->win_ones = std::all_of(w.taps, w.taps + n, [](float t) { return t == 1.0f; });
+  if (fold_pfb(e)) {
+    const int p = cfg->num_windows;
+    e->pfb_ring_ok = p == 4 || p == 8 || p == 16;
+    for (int k = 0; k < p; ++k) e->pfb_ring_ok &= (long long)cfg->window_starts[k] == (long long)k * n;
+    // whole frames, a multiple of 4 (even for the pair kernel, 16-byte aligned waterfall row offsets), at least 4
+    const long long chunk = std::max<long long>(4, (long long)KSA_PFB_CHUNK_BYTES / ((long long)n * 8) / 4 * 4);
+    e->pfb_chunk = (int)std::min<long long>(chunk, ((long long)cfg->max_frames + 3) / 4 * 4);
+  }
+  if (is_mixed_radix(n)) {
+    e->path = 6;
+    e->sub_n = n;
+    return;
+  }
+  e->path = n <= 16384 ? 0 : 2;
+  e->dif_radix = n <= 262144 ? 16 : n == 524288 ? 32 : 64;
+  const int sn = e->path == 0 ? n : n / e->dif_radix;     // the single-workgroup transform
+  e->sub_n = sn;
+  e->plan32 = (sn == 8192 || sn == 16384) && !exp_env("KSA_PLAN16");   // KSA_PLAN16 (experiments build): back to the 16-point plan
+  // Two frames per workgroup in packed fp32 (ksa_kernels_pair.hpp).  Measured against the one-frame kernel on MI355X
+  // (tools/pair_sweep.sh, hops 0.5 / 0.25 / 0.1): N = 1024 +14..+30 %, N = 2048 -3..-5 %, N = 4096 0..-5 % -- on by
+  // default for 1024 only.  KSA_PAIR_ALL enables it for 1024 .. 4096, KSA_NO_PAIR disables it (A/B switches).
+  e->pair_ok = e->path == 0 && !exp_env("KSA_NO_PAIR") && (sn == 1024 || (exp_env("KSA_PAIR_ALL") && sn >= 1024 && sn <= 4096));
+  e->k64_ok = sn == 64 && e->path == 0;     // the 8 x 8 plan of N = 64 (ksa_kernels64.hpp)
+  // constant hop of 1/2 or 1/4 of the transform: raw samples are carried over in registers
+  if (e->path == 0 && w.num_windows > 1 && n >= 1024) {
+    const int hop = w.starts[1] - w.starts[0];
+    bool same = true;
+    for (int i = 2; i < w.num_windows; ++i) same &= w.starts[i] - w.starts[i - 1] == hop;
+    if (same && (hop == n / 2 || hop == n / 4)) e->reuse_m = hop / (n / 16);
+  }
+  if (exp_env("KSA_NO_REUSE")) e->reuse_m = 0;   // A/B switch of the experiments build
+}
+
+template <typename T>
+int upload(T** dst, const std::vector<T>& src) { return upload(dst, src.data(), src.size()); }
+
+// 3. the tables of the plan (ksa_tables.hpp), built and uploaded
+int upload_tables(ksa_engine* e, const ksa_config* cfg, const WindowShape& w) {
+  namespace tab = ksa::tables;
+  const int n = cfg->fft_size, sn = e->sub_n;
+  if (fold_pfb(e)) {
+    if (upload(&e->d_pfb_starts, cfg->window_starts, (size_t)cfg->num_windows)) return 1;
+    if (upload(&e->d_pfb_taps, cfg->window, (size_t)cfg->num_windows * n)) return 1;
+  }
+  if (upload(&e->d_starts, w.starts, (size_t)w.num_windows)) return 1;
+  if (upload(&e->d_start_last, w.starts + w.num_windows - 1, 1)) return 1;
+  if (upload(&e->d_window, w.taps, (size_t)n)) return 1;
+  if (e->path == 6) {       // the plan's twiddles live in d_tw_mid
+    std::vector<float2> tw;
+    const std::string err = tab::plan_mr(n, &e->mr, &e->threads, &tw);
+    if (!err.empty()) return fail("%s", err.c_str());
+    if (upload(&e->d_tw_mid, tw)) return 1;
+    e->mr.tw = e->d_tw_mid;
+    return 0;
+  }
+  tab::Twiddles tw;
+  if (e->plan32) {
+    tw = tab::twiddles32(sn);
+    if (upload(&e->d_window32, tab::taps32(sn, e->path == 0 ? w.taps : nullptr))) return 1;
+  } else {
+    bool fused_mid = false, fused_last = false;     // the table layouts are the kernel's own choice
+    if (with_size(sn, [&](auto size) {
+          using Tune = ksa::Tune<decltype(size)::value>;
+          fused_mid = Tune::FUSED;
+          fused_last = Tune::FUSED_LAST;
+          return 0;
+        })) return 1;
+    tw = tab::twiddles16(sn, fused_mid, fused_last);
+  }
+  if (e->k64_ok) tw.mid = tab::twiddles64();     // the 4 x 16 plan of N = 64 has no middle pass, the slot is free
+  if (upload(&e->d_tw_mid, tw.mid)) return 1;
+  if (upload(&e->d_tw_last, tw.last)) return 1;
+  if (e->path == 2) {
+    if (upload(&e->d_dif_tw, tab::first_stage_twiddles(n, e->dif_radix))) return 1;
+    if (upload(&e->d_ones, std::vector<float>((size_t)sn, 1.0f))) return 1;     // the window was applied in the first stage
+    std::vector<int> sb((size_t)w.num_windows);
+    for (int i = 0; i < w.num_windows; ++i) sb[i] = i * sn;
+    if (upload(&e->d_starts_b, sb)) return 1;
+  }
+  return 0;
+}
+
+// 5. scratch (after the configure pass: the window split is sized by blocks_per_cu)
+int alloc_scratch(ksa_engine* e, int num_windows) {
+  const ksa_config& c = e->cfg;
+  const int n = c.fft_size;
+  const size_t nn = (size_t)n;
+  hipError_t he;
+  if (fold_pfb(e) && (he = hipMalloc(reinterpret_cast<void**>(&e->d_pfb_y), (size_t)e->pfb_chunk * n * sizeof(float2))) != hipSuccess)
+    return fail("hipMalloc(%zu) for the folded frames: %s", (size_t)e->pfb_chunk * n * sizeof(float2), hipGetErrorString(he));
+  if (e->path == 2) {
+    const int n1 = e->sub_n, nw = num_windows;
+    // scratch: Z = 8 N bytes per window.  Chunks of <= KSA_FS_SCRATCH_MB (default below) of Z
+    const size_t per_frame = (size_t)nw * n * sizeof(float2);
+    // 32-bit offsets inside the kernels: a pseudo frame is nwin*N1 complex points addressed in bytes
+    if ((long long)nw * n1 >= (1ll << 28)) return fail("num_windows %d x fft_size/16 %d exceeds 2^28 points per frame", nw, n1);
+    size_t budget = (size_t)KSA_DIF_SCRATCH_MB_DEFAULT << 20;
+    if (const char* mb = exp_env("KSA_FS_SCRATCH_MB")) {       // A/B switch of the experiments build; nonsense keeps the default
+      const long v = atol(mb);
+      if (v >= 1 && v <= (256l << 10)) budget = (size_t)v << 20;
+    }
+    e->dif_chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / per_frame), (size_t)c.max_frames);
+    e->dif_chunk = std::min(e->dif_chunk, 4095);               // gridDim.z of dif16_kernel, 16*chunk pseudo frames
+    if ((he = hipMalloc(reinterpret_cast<void**>(&e->d_dif_z), per_frame * e->dif_chunk)) != hipSuccess)
+      return fail("hipMalloc(%zu) for the first-stage scratch: %s", per_frame * e->dif_chunk, hipGetErrorString(he));
+    if ((he = hipMalloc(reinterpret_cast<void**>(&e->d_dif_y), (size_t)e->dif_chunk * n * 4)) != hipSuccess)
+      return fail("hipMalloc for the second-stage output: %s", hipGetErrorString(he));
+  }
+  e->max_chunks = (int)std::max<size_t>(1, std::min<size_t>(128, (64u << 20) / (3 * nn * 4)));
+#define ALLOC(ptr, bytes)                                                        \
+  if ((he = hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes))) != hipSuccess) \
+    return fail("hipMalloc(%zu) for %s: %s", (size_t)(bytes), #ptr, hipGetErrorString(he));
+  ALLOC(e->d_iq_stage, (size_t)c.full_size * 8);
+  ALLOC(e->d_frames, (size_t)c.max_frames * nn * 4);
+  ALLOC(e->d_part, (size_t)e->max_chunks * 3 * nn * 4);
+  ALLOC(e->d_xchg, (4 * nn + (size_t)KSA_HM_ROWS * c.hm_width) * 4);
+  e->d_partial = e->d_xchg;
+  if (c.hm_width) e->d_hm = e->d_xchg + 4 * nn;
+  ALLOC(e->d_state, 4 * nn * 4);
+  if (e->path != 6) ALLOC(e->d_parts, (size_t)e->num_cu * e->blocks_per_cu * (size_t)e->sub_n * 4);   // (path 6 has no window split)
+  if (c.scan_total_entries) {
+    ALLOC(e->d_scan_state, (size_t)4 * c.scan_total_entries * 4);
+    ALLOC(e->d_scan_hm, (size_t)KSA_HM_ROWS * c.scan_hm_width * 4);
+  }
+#undef ALLOC
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ksa_abi_version(void) { return KSA_ABI_VERSION; }
+const char* ksa_last_error(void) { return g_err.c_str(); }
+
+int ksa_create(const ksa_config* cfg, ksa_engine** out) {
+  if (!cfg || !out) return fail("null argument");
+  *out = nullptr;
+  if (validate_config(cfg)) return 1;
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail("device %d not present (%d visible)", cfg->device, ndev);
@@ -947,210 +1036,16 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   e->cfg.window_starts = nullptr;
   e->cfg.window = nullptr;
   e->num_cu = prop.multiProcessorCount;
-  int rc = 0;
   auto bail = [&](int r) { ksa_destroy(e); return r; };
 
-  // What the transform stage plans from and runs on.  KSA_CUMU_PFB: the inner shape -- one window at start 0 with all-ones
-  // taps over a folded frame of N samples; the caller's starts and taps [P][N] belong to the fold (ksa_pfb.hpp).
-  const std::vector<float> pfb_ones(pfb ? (size_t)n : 0, 1.0f);
+  const bool pfb = fold_pfb(e);
+  const std::vector<float> pfb_ones(pfb ? (size_t)cfg->fft_size : 0, 1.0f);
   const int32_t pfb_start0 = 0;
-  const int num_windows = pfb ? 1 : cfg->num_windows;
-  const int32_t* const window_starts = pfb ? &pfb_start0 : cfg->window_starts;
-  const float* const window = pfb ? pfb_ones.data() : cfg->window;
-  if (pfb) {
-    if ((rc = upload(&e->d_pfb_starts, cfg->window_starts, (size_t)cfg->num_windows))) return bail(rc);
-    if ((rc = upload(&e->d_pfb_taps, cfg->window, (size_t)cfg->num_windows * n))) return bail(rc);
-    const int p = cfg->num_windows;
-    e->pfb_ring_ok = p == 4 || p == 8 || p == 16;
-    for (int k = 0; k < p; ++k) e->pfb_ring_ok &= (long long)cfg->window_starts[k] == (long long)k * n;
-    // whole frames, a multiple of 4 (even for the pair kernel, 16-byte aligned waterfall row offsets), at least 4
-    const long long chunk = std::max<long long>(4, (long long)KSA_PFB_CHUNK_BYTES / ((long long)n * 8) / 4 * 4);
-    e->pfb_chunk = (int)std::min<long long>(chunk, ((long long)cfg->max_frames + 3) / 4 * 4);
-    hipError_t hp;
-    if ((hp = hipMalloc(reinterpret_cast<void**>(&e->d_pfb_y), (size_t)e->pfb_chunk * n * sizeof(float2))) != hipSuccess)
-      return bail(fail("hipMalloc(%zu) for the folded frames: %s", (size_t)e->pfb_chunk * n * sizeof(float2), hipGetErrorString(hp)));
-  }
-  if ((rc = upload(&e->d_starts, window_starts, (size_t)num_windows))) return bail(rc);
-  if ((rc = upload(&e->d_start_last, window_starts + num_windows - 1, 1))) return bail(rc);
-  if ((rc = upload(&e->d_window, window, (size_t)n))) return bail(rc);
-  e->win_ones = std::all_of(window, window + n, [](float w) { return w == 1.0f; });
-
-  if (mixed) {
-    e->path = 6;
-    e->sub_n = n;
-    std::vector<float2> tw;
-    if ((rc = plan_mr(n, &e->mr, &e->threads, &tw))) return bail(rc);
-    if ((rc = upload(&e->d_tw_mid, tw.data(), tw.size()))) return bail(rc);
-    e->mr.tw = e->d_tw_mid;
-    SpecParams dummy{};
-    if ((rc = launch_mr<ksa::FMT_C64>(e, dummy, true))) return bail(rc);
-    if ((rc = launch_mr<ksa::FMT_U8>(e, dummy, true))) return bail(rc);
-    if ((rc = launch_mr<ksa::FMT_S8>(e, dummy, true))) return bail(rc);
-    if ((rc = launch_mr<ksa::FMT_S16>(e, dummy, true))) return bail(rc);
-  } else {
-    e->path = n <= 16384 ? 0 : 2;
-    e->dif_radix = n <= 262144 ? 16 : n == 524288 ? 32 : 64;
-    const int sn = e->path == 0 ? n : n / e->dif_radix;     // the single-workgroup transform
-    e->sub_n = sn;
-    const int pt = 16, lpt = 4;   // 16 points per thread, radix-16 passes (an 8-point / radix-8 plan measured 20 % slower)
-    const bool fused_mid = tune_fused(sn), fused_last = tune_fused_last(sn);   // layouts must match ksa::Tune<N>
-    // twiddles in double, stored as float: middle passes [pt-1][p] each, last pass [pt-1][N/pt]
-    const int log2n = ksa::ilog2(sn);
-    const int m = (log2n + lpt - 1) / lpt;
-    const int r0 = 1 << (log2n - lpt * (m - 1));
-    std::vector<float2> mid, last;
-    int pcur = r0;
-    e->plan32 = (sn == 8192 || sn == 16384) && !exp_env("KSA_PLAN16");   // KSA_PLAN16 (experiments build): back to the 16-point plan
-    // Two frames per workgroup in packed fp32 (ksa_kernels_pair.hpp).  Measured against the one-frame kernel on MI355X
-    // (tools/pair_sweep.sh, hops 0.5 / 0.25 / 0.1): N = 1024 +14..+30 %, N = 2048 -3..-5 %, N = 4096 0..-5 % -- on by
-    // default for 1024 only.  KSA_PAIR_ALL enables it for 1024 .. 4096, KSA_NO_PAIR disables it (A/B switches).
-    e->pair_ok = e->path == 0 && !exp_env("KSA_NO_PAIR") && (sn == 1024 || (exp_env("KSA_PAIR_ALL") && sn >= 1024 && sn <= 4096));
-    if (e->plan32) {
-      // folded twiddles of dft16_fused for a base twiddle of `beta` turns: w^4, w^8, w^12, then w^n2 * W16^(n2*k1)
-      auto fused15 = [](double beta, int e) {
-        double turns;
-        if (e < 3) turns = 4.0 * (e + 1) * beta;
-        else { const int k1 = (e - 3) / 3, n2 = (e - 3) % 3 + 1; turns = n2 * beta + (double)(n2 * k1) / 16.0; }
-        const double ang = -2.0 * M_PI * turns;
-        return make_float2((float)std::cos(ang), (float)std::sin(ang));
-      };
-      const int r1 = sn == 16384 ? 32 : 16, lth = sn / 32;
-      if (r1 == 32) {          // middle pass radix 32, p = 32: [31][32] = w^16 | fused15(k/1024) | fused15(k/1024 + 1/32)
-        mid.resize((size_t)31 * 32);
-        for (int k = 0; k < 32; ++k) {
-          const double beta = (double)k / 1024.0;
-          const double a16 = -2.0 * M_PI * 16.0 * beta;
-          mid[k] = make_float2((float)std::cos(a16), (float)std::sin(a16));
-          for (int ee = 0; ee < 15; ++ee) {
-            mid[(size_t)(1 + ee) * 32 + k] = fused15(beta, ee);
-            mid[(size_t)(16 + ee) * 32 + k] = fused15(beta + 1.0 / 32.0, ee);
-          }
-        }
-      } else {                 // middle pass radix 16, p = 32: [15][32] = fused15(k/512)
-        mid.resize((size_t)15 * 32);
-        for (int k = 0; k < 32; ++k)
-          for (int ee = 0; ee < 15; ++ee) mid[(size_t)ee * 32 + k] = fused15((double)k / 512.0, ee);
-      }
-      // last pass radix 16, two butterflies per thread, k = i = l + b*L: [(b*15 + e)][L]
-      last.resize((size_t)30 * lth);
-      for (int b = 0; b < 2; ++b)
-        for (int ee = 0; ee < 15; ++ee)
-          for (int l = 0; l < lth; ++l) last[(size_t)(b * 15 + ee) * lth + l] = fused15((double)(l + b * lth) / (double)sn, ee);
-    }
-    for (int s = 1; s < m && !e->plan32; ++s) {
-      std::vector<float2>& dst = s < m - 1 ? mid : last;
-      const bool fused = s < m - 1 ? fused_mid : fused_last;
-      if (fused) {
-        // rows of dft16_fused: w^4, w^8, w^12, then c[n2][k1] = w^n2 * W16^(n2*k1) for k1 = 0..3, n2 = 1..3
-        for (int e = 0; e < 15; ++e)
-          for (int k = 0; k < pcur; ++k) {
-            const double base = (double)k / ((double)pcur * 16.0);
-            double turns;
-            if (e < 3) turns = 4.0 * (e + 1) * base;
-            else { const int k1 = (e - 3) / 3, n2 = (e - 3) % 3 + 1; turns = n2 * base + (double)(n2 * k1) / 16.0; }
-            const double ang = -2.0 * M_PI * turns;
-            dst.push_back(make_float2((float)std::cos(ang), (float)std::sin(ang)));
-          }
-      } else {
-        for (int t = 1; t < pt; ++t)
-          for (int k = 0; k < pcur; ++k) {
-            const double ang = -2.0 * M_PI * (double)t * (double)k / ((double)pcur * pt);
-            dst.push_back(make_float2((float)std::cos(ang), (float)std::sin(ang)));
-          }
-      }
-      pcur *= pt;
-    }
-    if (e->plan32) {
-      // taps (or, behind a first stage, the all-ones table) in the 32-point kernel's load order: [q4][l][j] = w[l + L*(4*q4 + j)]
-      const int lth = sn / 32;
-      std::vector<float> w32((size_t)sn);
-      for (int q4 = 0; q4 < 8; ++q4)
-        for (int l = 0; l < lth; ++l)
-          for (int j = 0; j < 4; ++j)
-            w32[((size_t)q4 * lth + l) * 4 + j] = e->path == 0 ? window[l + lth * (4 * q4 + j)] : 1.0f;
-      if ((rc = upload(&e->d_window32, w32.data(), w32.size()))) return bail(rc);
-    }
-    if (sn == 64 && e->path == 0) {
-      // the 8 x 8 plan of N = 64 (ksa_kernels64.hpp): W64^(m k1) as [m][k1]; the 4 x 16 plan has no middle pass, the slot is free
-      e->k64_ok = true;
-      mid.resize(64);
-      for (int mm = 0; mm < 8; ++mm)
-        for (int k1 = 0; k1 < 8; ++k1) {
-          const double ang = -2.0 * M_PI * (double)(mm * k1) / 64.0;
-          mid[(size_t)mm * 8 + k1] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-        }
-    }
-    if ((rc = upload(&e->d_tw_mid, mid.data(), mid.size()))) return bail(rc);
-    if ((rc = upload(&e->d_tw_last, last.data(), last.size()))) return bail(rc);
-    // constant hop of 1/2 or 1/4 of the transform: raw samples are carried over in registers
-    if (e->path == 0 && num_windows > 1 && n >= 1024) {
-      const int hop = window_starts[1] - window_starts[0];
-      bool same = true;
-      for (int i = 2; i < num_windows; ++i) same &= window_starts[i] - window_starts[i - 1] == hop;
-      if (same && (hop == n / 2 || hop == n / 4)) e->reuse_m = hop / (n / pt);
-    }
-    if (exp_env("KSA_NO_REUSE")) e->reuse_m = 0;   // A/B switch of the experiments build
-    SpecParams dummy{};
-    dummy.nwin = num_windows;
-    if ((rc = launch_spec_n<ksa::FMT_C64>(e, dummy, true))) return bail(rc);
-    if ((rc = launch_spec_n<ksa::FMT_U8>(e, dummy, true))) return bail(rc);
-    if ((rc = launch_spec_n<ksa::FMT_S8>(e, dummy, true))) return bail(rc);
-    if ((rc = launch_spec_n<ksa::FMT_S16>(e, dummy, true))) return bail(rc);
-    if (e->path == 2) {
-      const int n1 = sn, nw = num_windows;
-      // first-stage output twiddles W_N^(n1*e), e = 1,2,3,4,8,12 (float64-generated); w^k2 = w^(k2&3) * w^(k2&12)
-      static const int ex[9] = {1, 2, 3, 4, 8, 12, 16, 32, 48};
-      const int nrows = e->dif_radix == 16 ? 6 : 9;
-      std::vector<float2> tw((size_t)nrows * n1);
-      for (int r = 0; r < nrows; ++r)
-        for (int k = 0; k < n1; ++k) {
-          const double ang = -2.0 * M_PI * (double)ex[r] * (double)k / (double)n;
-          tw[(size_t)r * n1 + k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-        }
-      if ((rc = upload(&e->d_dif_tw, tw.data(), tw.size()))) return bail(rc);
-      std::vector<float> ones((size_t)n1, 1.0f);
-      if ((rc = upload(&e->d_ones, ones.data(), ones.size()))) return bail(rc);
-      std::vector<int> sb((size_t)nw);
-      for (int w = 0; w < nw; ++w) sb[w] = w * n1;
-      if ((rc = upload(&e->d_starts_b, sb.data(), sb.size()))) return bail(rc);
-      // scratch: Z = 8 N bytes per window.  Chunks of <= KSA_FS_SCRATCH_MB (default below) of Z
-      const size_t per_frame = (size_t)nw * n * sizeof(float2);
-      // 32-bit offsets inside the kernels: a pseudo frame is nwin*N1 complex points addressed in bytes
-      if ((long long)nw * n1 >= (1ll << 28)) return bail(fail("num_windows %d x fft_size/16 %d exceeds 2^28 points per frame", nw, n1));
-      size_t budget = (size_t)KSA_DIF_SCRATCH_MB_DEFAULT << 20;
-      if (const char* mb = exp_env("KSA_FS_SCRATCH_MB")) {       // A/B switch of the experiments build; nonsense keeps the default
-        const long v = atol(mb);
-        if (v >= 1 && v <= (256l << 10)) budget = (size_t)v << 20;
-      }
-      e->dif_chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / per_frame), (size_t)cfg->max_frames);
-      e->dif_chunk = std::min(e->dif_chunk, 4095);               // gridDim.z of dif16_kernel, 16*chunk pseudo frames
-      hipError_t he2;
-      if ((he2 = hipMalloc(reinterpret_cast<void**>(&e->d_dif_z), per_frame * e->dif_chunk)) != hipSuccess)
-        return bail(fail("hipMalloc(%zu) for the first-stage scratch: %s", per_frame * e->dif_chunk, hipGetErrorString(he2)));
-      if ((he2 = hipMalloc(reinterpret_cast<void**>(&e->d_dif_y), (size_t)e->dif_chunk * n * 4)) != hipSuccess)
-        return bail(fail("hipMalloc for the second-stage output: %s", hipGetErrorString(he2)));
-    }
-  }
-
-  const size_t nn = (size_t)n;
-  e->max_chunks = (int)std::max<size_t>(1, std::min<size_t>(128, (64u << 20) / (3 * nn * 4)));
-  hipError_t he;
-#define ALLOC(ptr, bytes)                                                        \
-  if ((he = hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes))) != hipSuccess) \
-    return bail(fail("hipMalloc(%zu) for %s: %s", (size_t)(bytes), #ptr, hipGetErrorString(he)));
-  ALLOC(e->d_iq_stage, (size_t)cfg->full_size * 8);
-  ALLOC(e->d_frames, (size_t)cfg->max_frames * nn * 4);
-  ALLOC(e->d_part, (size_t)e->max_chunks * 3 * nn * 4);
-  ALLOC(e->d_xchg, (4 * nn + (size_t)KSA_HM_ROWS * cfg->hm_width) * 4);
-  e->d_partial = e->d_xchg;
-  if (cfg->hm_width) e->d_hm = e->d_xchg + 4 * nn;
-  ALLOC(e->d_state, 4 * nn * 4);
-  if (e->path != 6) ALLOC(e->d_parts, (size_t)e->num_cu * e->blocks_per_cu * (size_t)e->sub_n * 4);   // (path 6 has no window split)
-  if (cfg->scan_total_entries) {
-    ALLOC(e->d_scan_state, (size_t)4 * cfg->scan_total_entries * 4);
-    ALLOC(e->d_scan_hm, (size_t)KSA_HM_ROWS * cfg->scan_hm_width * 4);
-  }
-#undef ALLOC
+  const WindowShape w = pfb ? WindowShape{1, &pfb_start0, pfb_ones.data()} : WindowShape{cfg->num_windows, cfg->window_starts, cfg->window};
+  choose_plan(e, cfg, w);
+  if (upload_tables(e, cfg, w)) return bail(1);
+  if (configure_kernels(e, w.num_windows)) return bail(1);
+  if (alloc_scratch(e, w.num_windows)) return bail(1);
   if (ksa_reset_state(e)) return bail(1);
   if (cfg->scan_total_entries && scan_reset(e)) return bail(1);
   if (hipStreamSynchronize(e->stream) != hipSuccess) return bail(fail("initial sync failed"));
@@ -1208,7 +1103,7 @@ int ksa_curscan_dev(ksa_engine* e, const void* iq_dev, int32_t fmt, int64_t fram
   if (out_mode < KSA_OUT_LINEAR || out_mode > KSA_OUT_DB_CLIP) return fail("unknown out_mode %d", out_mode);
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(e->cfg.device));
-  return run_spectrum(e, iq_dev, fmt, frame_stride, nframes, out_mode, out_dev, false, nullptr);
+  return run_spectrum(e, {iq_dev, fmt, frame_stride, nframes}, out_mode, out_dev, false, nullptr);
 }
 
 static int curscan_host(ksa_engine* e, const void* iq_host, int fmt, float* mag_host) {
@@ -1216,7 +1111,7 @@ static int curscan_host(ksa_engine* e, const void* iq_host, int fmt, float* mag_
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(e->cfg.device));
   HIP_OK(hipMemcpyAsync(e->d_iq_stage, iq_host, (size_t)e->cfg.full_size * sample_bytes(fmt), hipMemcpyHostToDevice, e->stream));
-  if (run_spectrum(e, e->d_iq_stage, fmt, 0, 1, KSA_OUT_LINEAR, e->d_frames, false, nullptr)) return 1;
+  if (run_spectrum(e, {e->d_iq_stage, fmt, 0, 1}, KSA_OUT_LINEAR, e->d_frames, false, nullptr)) return 1;
   HIP_OK(hipMemcpyAsync(mag_host, e->d_frames, (size_t)e->cfg.fft_size * 4, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   return 0;
@@ -1232,7 +1127,7 @@ int ksa_frames_dev(ksa_engine* e, const void* iq_dev, int32_t fmt, int64_t frame
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(e->cfg.device));
   float* db = cur_db_dev ? cur_db_dev : e->d_frames;
-  if (run_spectrum(e, iq_dev, fmt, frame_stride, nframes, KSA_OUT_DB, db, e->cfg.hm_width > 0, hm_rows_dev)) return 1;
+  if (run_spectrum(e, {iq_dev, fmt, frame_stride, nframes}, KSA_OUT_DB, db, e->cfg.hm_width > 0, hm_rows_dev)) return 1;
   if (run_accumulate(e, db, nframes, first_index, total_frames)) return 1;
   e->pending_frames = nframes;
   if (commit) return do_commit(e, total_frames, nframes);
@@ -1288,8 +1183,8 @@ static int frames_host(ksa_engine* e, const void* iq_host, int fmt, int nframes,
                           hipMemcpyHostToDevice, e->copy_stream));
     HIP_OK(hipEventRecord(e->ev_slot_copied[s], e->copy_stream));
     HIP_OK(hipStreamWaitEvent(e->stream, e->ev_slot_copied[s], 0));
-    if (run_spectrum(e, e->d_slot[s], fmt, c.full_size, nf, KSA_OUT_DB, e->d_frames + (size_t)f0 * n, c.hm_width > 0,
-                     rows_dev ? rows_dev + (size_t)f0 * c.hm_width : nullptr, f0, nframes)) return 1;
+    if (run_spectrum(e, {e->d_slot[s], fmt, c.full_size, nf, f0, nframes}, KSA_OUT_DB, e->d_frames + (size_t)f0 * n, c.hm_width > 0,
+                     rows_dev ? rows_dev + (size_t)f0 * c.hm_width : nullptr)) return 1;
     HIP_OK(hipEventRecord(e->ev_slot_read[s], e->stream));
   }
   if (run_accumulate(e, e->d_frames, nframes, first_index, total)) return 1;
@@ -1806,7 +1701,7 @@ int ksa_scan_stitch_passes_dev(ksa_engine* e, const float* step_db_dev, int32_t 
 // step_ok entry is 0 is replaced by the dummy band: ones(fftSize) through the same two steps (K:637-641)
 static int scan_spectra(ksa_engine* e, const void* iq_dev, int fmt, long long frame_stride, int frames, const uint8_t* step_ok,
                         float* out_dev) {
-  if (run_spectrum(e, iq_dev, fmt, frame_stride, frames, KSA_OUT_DB_CLIP, out_dev, false, nullptr)) return 1;
+  if (run_spectrum(e, {iq_dev, fmt, frame_stride, frames}, KSA_OUT_DB_CLIP, out_dev, false, nullptr)) return 1;
   if (step_ok) {
     const float v = (float)(10.0 * std::log10(std::max(1.0, (double)e->cfg.min_amp)) - (double)e->cfg.gain);
     for (long long s = 0; s < frames; ++s)

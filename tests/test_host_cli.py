@@ -300,7 +300,7 @@ def test_every_entry_point_that_touches_hip_selects_its_engines_device():
     hdr = open(os.path.join(root, "include", "ksa.h")).read()
     exported = set(re.findall(r"\b(ksa_[a-z0-9_]+)\s*\(", hdr))
     assert exported <= set(fns) | {"ksa_abi_version", "ksa_last_error"}, exported - set(fns)
-    helpers = r"run_spectrum|run_accumulate|do_commit|fill|scan_reset|join_side|levels_to_scratch|copy_ring_rows|scan_stitch|gather_all|upload|ensure|scan_spectra|copy_d2d|ensure_events"
+    helpers = r"run_spectrum|run_accumulate|do_commit|fill|scan_reset|join_side|levels_to_scratch|copy_ring_rows|scan_stitch|gather_all|upload|ensure|scan_spectra|copy_d2d|ensure_events|upload_tables|configure_kernels|alloc_scratch"
     touches = re.compile(r"\bhip[A-Z]\w*\s*\(|\bHIP_OK\b|hipLaunchKernelGGL|\b(?:%s)\s*\(" % helpers)
     checked = 0
     for name in sorted(exported & set(fns)):

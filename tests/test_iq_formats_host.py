@@ -46,11 +46,25 @@ def test_header_binding_and_package_agree_and_the_abi_is_untouched():
 def test_the_library_knows_the_sample_sizes_and_instantiates_every_load_stage():
     src = open(os.path.join(ROOT, "prgs-sdr-kspecanal_amd", "csrc", "ksa_api.hip")).read()
     assert re.search(r"size_t sample_bytes\(int fmt\) \{ return fmt == KSA_FMT_C64 \? 8 : fmt == KSA_FMT_S16 \? 4 : 2; \}", src)
-    for needle in ("launch_spec_n<ksa::FMT_S8>(e, dummy, true)", "launch_spec_n<ksa::FMT_S16>(e, dummy, true)",
-                   "launch_mr<ksa::FMT_S8>(e, dummy, true)", "launch_mr<ksa::FMT_S16>(e, dummy, true)",
-                   "dif16_kernel<ksa::FMT_S8>", "dif16_kernel<ksa::FMT_S16>", "dif_wide_kernel<ksa::FMT_S8, 32>",
-                   "dif_wide_kernel<ksa::FMT_S16, 32>", "dif_wide_kernel<ksa::FMT_S8, 64>", "dif_wide_kernel<ksa::FMT_S16, 64>"):
-        assert needle in src, needle
+    # one list of formats: with_fmt dispatches over it, and it names all four
+    m = re.search(r"using Formats = Ints<([^>]*)>;", src)
+    assert m and sorted(t.strip() for t in m.group(1).split(",")) == ["ksa::FMT_C64", "ksa::FMT_S16", "ksa::FMT_S8", "ksa::FMT_U8"]
+    assert re.search(r"int with_fmt\(int fmt, F&& f\) \{\s*const int rc = dispatch\(fmt, Formats\{\}, f\);", src)
+    # the configure pass of both plan families walks that list
+    cfg = src[src.index("int configure_kernels("):]
+    cfg = cfg[:cfg.index("\n}\n")]
+    assert "for_each_fmt(Formats{}, [&](auto f)" in cfg and "constexpr int FMT = decltype(f)::value;" in cfg
+    for needle in ("launch_spec_n<FMT>(e, dummy, true)", "launch_mr<FMT>(e, dummy, true)"):
+        assert needle in cfg, needle
+    # ... and so do the launches: both plan families, the first stage at every radix, the polyphase fold
+    dif = src[src.index("int run_dif16("):]
+    dif = dif[:dif.index("\n}\n")]
+    assert "using Radices = Ints<16, 32, 64>;" in src and "with_fmt(fmt, [&](auto f)" in dif and "dispatch(R, Radices{}," in dif
+    for needle in ("ksa::dif16_kernel<FMT>", "ksa::dif_wide_kernel<FMT, RX>"):
+        assert needle in dif, needle
+    for needle in ("launch_spec_n<decltype(fmt)::value>(e, p, false)", "launch_mr<decltype(fmt)::value>(e, p, false)",
+                   "launch_pfb_fmt<decltype(fmt)::value>(e, a, ring)"):
+        assert "with_fmt(f.fmt, [&](auto fmt) { return %s; })" % needle in src, needle
 
 
 # ------------------------------------------------------------------------------------------------ sources
