@@ -62,6 +62,26 @@ enum { KSA_CUMU_PSD = 4 };
  * ksa_create ("unknown cumu_mode 5"). */
 enum { KSA_CUMU_PFB = 5 };
 #define KSA_PFB_MAX_TAPS 16
+/* Integrating polyphase spectrometer: the polyphase fold, then |X|^2, then the sum over the K consecutive spectra a block holds
+ * (the reference has no counterpart).  Per captured block, with N = fft_size, P = num_windows (1 <= P <= KSA_PFB_MAX_TAPS),
+ * window = host[P*N] and window_starts = host[P]:
+ *   K        = (full_size - max_k(window_starts[k]) - N) / N + 1          (integer division; >= 1 by the check of the starts)
+ *   y_j[n]   = sum over k < P, in the order k = 0, 1, ..., of x[j*N + window_starts[k] + n] * window[k*N + n]     j = 0 .. K-1
+ *   out[bin] = mag_scale * sum over j < K of |FFT_N(y_j)[bin]|^2                                              (fftshifted)
+ * The sub-frames advance by exactly N samples (the critically sampled bank: no phase rotation is needed); a tail of fewer than
+ * N samples is ignored.  K comes from full_size, so full_size is part of the geometry for the `_dev` entry points too: a block
+ * must hold full_size samples from its start.  frame_stride is free as for every other fold; frame_stride = K*N makes
+ * consecutive blocks share P-1 segments of one continuous stream.  mag_scale is the caller's: 1 / (Fs * sum(window^2) * K) with
+ * Fs = 2 puts white noise at the level KSA_CUMU_PSD reports for it (a unit-variance complex stream reads 0.5).  KSA_OUT_LINEAR
+ * returns that power; KSA_OUT_DB / KSA_OUT_DB_CLIP apply LogNoGain / Clip2MinAmp to it unchanged, as for KSA_CUMU_PSD.  A NaN
+ * sample makes every bin of its block NaN and leaves other blocks alone; an all-zero block gives -inf dB (KSA_OUT_DB) or 0
+ * (KSA_OUT_DB_CLIP, min_amp 0).  One block of folded sub-frames, K*N*8 bytes, must fit the library's fold + transform chunk
+ * (256 MiB) and is refused otherwise.  Every fft_size, every sample format and every entry point that runs the spectrum stage
+ * accepts it; the state, the waterfall, the plot hand-off and the multi-engine merges consume per-block spectra and are
+ * unchanged.  The transform stage is what a KSA_CUMU_PSD engine of K rectangular windows at hop N runs on complex64 frames (what
+ * the path of the kernel-info entry point describes), whatever the input format.  The layout and the calls are unchanged, so the
+ * ABI number is too: a library without this mode refuses it in the create call ("unknown cumu_mode 6"). */
+enum { KSA_CUMU_PFB_PSD = 6 };
 /* IQ sample formats: complex64 (what sdr.read_samples hands over, narrowed from K:335's complex128)
  * and the dongle's native interleaved uint8 I,Q (pyrtlsdr packed_bytes_to_iq; K:301, K:339, K:346) */
 enum { KSA_FMT_C64 = 0, KSA_FMT_U8 = 1 };
@@ -90,10 +110,10 @@ typedef struct ksa_config {
                                    (the mixed-radix path; the layout and the calls are unchanged, so the ABI number is too:
                                    a library without that path refuses such sizes in ksa_create) */
   int32_t full_size;            /* d['fullSize'] K:926-929: samples per captured block */
-  int32_t num_windows;          /* windows actually transformed (K:385-390); KSA_CUMU_PFB: the tap count P */
+  int32_t num_windows;          /* windows actually transformed (K:385-390); KSA_CUMU_PFB / KSA_CUMU_PFB_PSD: the tap count P */
   const int32_t* window_starts; /* host[num_windows]: iStart = int(i*fftSize*nonOverlap) K:386 */
-  const float* window;          /* host[fft_size]: d['theWin'] K:932-936; the length depends on the mode: KSA_CUMU_PFB
-                                   reads host[num_windows*fft_size], the prototype filter */
+  const float* window;          /* host[fft_size]: d['theWin'] K:932-936; the length depends on the mode: KSA_CUMU_PFB and
+                                   KSA_CUMU_PFB_PSD read host[num_windows*fft_size], the prototype filter */
   double mag_scale;             /* 2*winAdj/fftSize with winAdj = N/sum(win): K:373, K:391 */
   int32_t cumu_mode;            /* KSA_CUMU_*: within-block fold K:392-395 */
   float gain;                   /* d['gain'] subtracted by LogNoGain K:109 */

@@ -12,6 +12,7 @@ ABI_VERSION = 5
 HM_ROWS = 128
 CUMU = {"RAW": 0, "AVG": 1, "MAX": 2, "MIN": 3, "PSD": 4}
 CUMU_PFB = 5                # KSA_CUMU_PFB: the polyphase front end; chosen by SpectrumEngine(pfb_taps=...), not by a fold name
+CUMU_PFB_PSD = 6            # KSA_CUMU_PFB_PSD: the integrating polyphase spectrometer; chosen by SpectrumEngine(pfb_spectra=...)
 PFB_MAX_TAPS = 16           # KSA_PFB_MAX_TAPS
 FMT_C64, FMT_U8 = 0, 1
 FMT_S8, FMT_S16 = 2, 3      # interleaved signed int8 (b / 128) and little-endian int16 (b / 32768) I,Q

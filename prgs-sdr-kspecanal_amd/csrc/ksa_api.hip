@@ -153,6 +153,9 @@ struct ksa_engine {
   float2* d_pfb_y = nullptr;    // [pfb_chunk][N] folded frames
   int pfb_chunk = 0;            // frames per fold + transform chunk (a multiple of 4)
   bool pfb_ring_ok = false;     // starts[k] == k*N and P in {4, 8, 16}: the ring kernel may serve frame_stride == N
+  // KSA_CUMU_PFB_PSD: every block folds into pfb_sub (K) sub-frames, d_pfb_y is [pfb_chunk][K][N] and the inner shape K
+  // rectangular windows at j*N over a folded frame of K*N samples (1 on a KSA_CUMU_PFB engine: one folded frame per block)
+  int pfb_sub = 1;
   // bookkeeping
   long long frames_seen = 0;
   int hm_index = 0;
@@ -196,9 +199,14 @@ int plan_of(const ksa_engine* e, const SpecParams& p) { return std::max(p.nframe
 
 // KSA_CUMU_PSD engines run the CUMU_PSD instantiation of every spectrum kernel (a template constant everywhere, also where the
 // other folds branch at run time) with SpecParams::cumu = CUMU_AVG: the combines and the output stage of the two are the same.
-bool fold_psd(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PSD; }
+// A KSA_CUMU_PFB_PSD engine's transform stage is that of a KSA_CUMU_PSD engine of K rectangular windows at hop N on complex64.
+bool fold_psd(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PSD || e->cfg.cumu_mode == KSA_CUMU_PFB_PSD; }
 // KSA_CUMU_PFB engines fold in the time domain (ksa_pfb.hpp) and run the AVG instantiations on one window per folded frame.
 bool fold_pfb(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PFB; }
+// KSA_CUMU_PFB_PSD engines fold every block into K sub-frames in the time domain and run the PSD instantiations over them.
+bool fold_pfb_psd(const ksa_engine* e) { return e->cfg.cumu_mode == KSA_CUMU_PFB_PSD; }
+// either of the two: a fold stage in front of the transform stage
+bool fold_time(const ksa_engine* e) { return fold_pfb(e) || fold_pfb_psd(e); }
 // bytes per IQ sample of a KSA_FMT_* value
 size_t sample_bytes(int fmt) { return fmt == KSA_FMT_C64 ? 8 : fmt == KSA_FMT_S16 ? 4 : 2; }
 
@@ -531,7 +539,37 @@ int launch_pfb_fmt(ksa_engine* e, const ksa::PfbParams& a, bool ring) {
   return 0;
 }
 
-// One fold launch of a KSA_CUMU_PFB engine: the caller's frames `f` (at most pfb_chunk) -> d_pfb_y[nframes][N].
+// KSA_CUMU_PFB_PSD: the block-aware kernels, a.f.nframes blocks of a.nsub sub-frames each.
+template <int FMT>
+int launch_pfbpsd_fmt(ksa_engine* e, const ksa::PfbPsdParams& a, bool ring) {
+  const long long per = a.f.n / ksa::PFB_COLS;
+  if (ring) {
+    const long long slices = (a.nsub + ksa::PFB_SLICE_FRAMES - 1) / ksa::PFB_SLICE_FRAMES;
+    const long long items = per * slices * a.f.nframes;
+    const dim3 grid((unsigned)((items + ksa::PFB_THREADS - 1) / ksa::PFB_THREADS));
+    // (only the (format, P) pairs the rule can select are instantiated: ksa::pfbpsd_ring_pays)
+    bool launched = false;
+    dispatch(a.f.ntaps, Ints<4, 8, 16>{}, [&](auto taps) {
+      constexpr int P = decltype(taps)::value;
+      if constexpr (ksa::pfbpsd_ring_pays(FMT, P)) {
+        hipLaunchKernelGGL((ksa::pfbpsd_ring_kernel<FMT, P>), grid, dim3(ksa::PFB_THREADS), 0, e->stream, a);
+        launched = true;
+      }
+      return 0;
+    });
+    if (!launched) return fail("no block ring kernel for format %d at %d taps", FMT, a.f.ntaps);
+  } else {
+    const long long items = per * a.nsub * a.f.nframes;
+    const long long blocks = (items + ksa::PFB_THREADS - 1) / ksa::PFB_THREADS;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)e->num_cu * 32)));
+    hipLaunchKernelGGL(ksa::pfbpsd_fold_kernel<FMT>, grid, dim3(ksa::PFB_THREADS), 0, e->stream, a);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// One fold launch of a KSA_CUMU_PFB / KSA_CUMU_PFB_PSD engine: the caller's frames `f` (at most pfb_chunk) ->
+// d_pfb_y[nframes][N], or d_pfb_y[nframes][K][N] on a KSA_CUMU_PFB_PSD engine.
 int launch_pfb(ksa_engine* e, const Frames& f) {
   const ksa_config& c = e->cfg;
   ksa::PfbParams a{};
@@ -545,6 +583,13 @@ int launch_pfb(ksa_engine* e, const Frames& f) {
   a.u8_offset = c.u8_offset;
   a.u8_inv_scale = 1.0f / c.u8_scale;
   a.y = e->d_pfb_y;
+  if (fold_pfb_psd(e)) {
+    // The sliding happens inside a block, so the ring form serves every frame_stride (KSA_PFB_NO_RING: A/B switch of the
+    // experiments build).
+    const bool ring = e->pfb_ring_ok && ksa::pfbpsd_ring_pays(f.fmt, c.num_windows) && !exp_env("KSA_PFB_NO_RING");
+    const ksa::PfbPsdParams b{a, e->pfb_sub};
+    return with_fmt(f.fmt, [&](auto fmt) { return launch_pfbpsd_fmt<decltype(fmt)::value>(e, b, ring); });
+  }
   // The ring kernel where it measured faster than the generic one at stride N (profiles/pfb_sweep.txt): it saves (P - 1)
   // re-reads of a sample per output point and pays with P - 1 warm-up loads per slice and fewer, longer threads; from 12 saved
   // bytes up it won (complex64 P >= 4, 2-byte samples P >= 8), below that the generic kernel's re-reads hit in cache and it lost.
@@ -661,17 +706,18 @@ int check_frames(const ksa_engine* e, const Frames& f, const float* out, const f
 }
 
 // Spectrum stage for a batch: the single-workgroup LDS FFT, behind a radix-16 / 32 / 64 first stage for N > 16384.
-// `fold` (KSA_CUMU_PFB): the fold launch that fills f.iq for these frames, enqueued inside the profiled interval.
+// `fold` (KSA_CUMU_PFB, KSA_CUMU_PFB_PSD): the fold launch that fills f.iq for these frames, enqueued inside the profiled
+// interval; the frames are then folded ones of pfb_sub rectangular windows each (one on a KSA_CUMU_PFB engine).
 int run_transform(ksa_engine* e, const Frames& f, int out_mode, float* out, bool with_hm, float* hm_rows, const Frames* fold) {
   const ksa_config& c = e->cfg;
   if (check_frames(e, f, out, hm_rows)) return 1;
   SpecParams p{};
   p.iq = f.iq;
   p.frame_stride = f.stride;
-  p.frame_len = fold ? c.fft_size : c.full_size;
+  p.frame_len = fold ? e->pfb_sub * c.fft_size : c.full_size;
   p.nframes = f.nframes;
   const bool raw = c.cumu_mode == KSA_CUMU_RAW;
-  p.nwin = (raw || fold) ? 1 : c.num_windows;  // RAW keeps the last window only (K:135-136); a folded frame is one window
+  p.nwin = fold ? e->pfb_sub : raw ? 1 : c.num_windows;  // RAW keeps the last window only (K:135-136); a folded frame is one window (KSA_CUMU_PFB_PSD: K)
   p.starts = raw ? e->d_start_last : e->d_starts;
 #if defined(KSA32_TAPS_X4) && !KSA32_TAPS_X4
   p.window = e->d_window;
@@ -741,17 +787,18 @@ int run_transform(ksa_engine* e, const Frames& f, int out_mode, float* out, bool
 
 // Spectrum stage of every entry point.  KSA_CUMU_PFB: the batch runs in chunks of pfb_chunk frames -- fold into the engine's
 // scratch, then the transform on that scratch as complex64 frames of N samples at stride N -- and every chunk takes the whole
-// batch's launch plan and ring rows (batch_first / batch_frames), exactly as the slots of a host batch do.
+// batch's launch plan and ring rows (batch_first / batch_frames), exactly as the slots of a host batch do.  KSA_CUMU_PFB_PSD:
+// the same in whole blocks, a folded frame being the K sub-frames of one block (K*N samples at stride K*N).
 int run_spectrum(ksa_engine* e, Frames f, int out_mode, float* out, bool with_hm, float* hm_rows) {
   if (f.batch_frames < 1) f.batch_frames = f.nframes;
-  if (!fold_pfb(e)) return run_transform(e, f, out_mode, out, with_hm, hm_rows, nullptr);
+  if (!fold_time(e)) return run_transform(e, f, out_mode, out, with_hm, hm_rows, nullptr);
   const ksa_config& c = e->cfg;
   if (check_frames(e, f, out, hm_rows)) return 1;
   const size_t n = (size_t)c.fft_size;
   for (int f0 = 0; f0 < f.nframes; f0 += e->pfb_chunk) {
     const int nf = std::min(e->pfb_chunk, f.nframes - f0);
     const Frames fold{static_cast<const unsigned char*>(f.iq) + (size_t)f0 * (size_t)f.stride * sample_bytes(f.fmt), f.fmt, f.stride, nf};
-    const Frames folded{e->d_pfb_y, KSA_FMT_C64, c.fft_size, nf, f.batch_first + f0, f.batch_frames};
+    const Frames folded{e->d_pfb_y, KSA_FMT_C64, (long long)e->pfb_sub * c.fft_size, nf, f.batch_first + f0, f.batch_frames};
     if (run_transform(e, folded, out_mode, out + (size_t)f0 * n, with_hm, hm_rows ? hm_rows + (size_t)f0 * c.hm_width : nullptr, &fold)) return 1;
   }
   return 0;
@@ -842,6 +889,14 @@ int ensure(T** ptr, size_t* cap, size_t count) {
   return 0;
 }
 
+// KSA_CUMU_PFB_PSD: K, the sub-frames of fft_size samples a block holds behind its last segment start (include/ksa.h); at
+// least 1 once the starts have passed their check against full_size.
+int pfb_subframes(const ksa_config* cfg) {
+  const int n = cfg->fft_size;
+  const int last = *std::max_element(cfg->window_starts, cfg->window_starts + cfg->num_windows);
+  return (cfg->full_size - last - n) / n + 1;
+}
+
 // ---- ksa_create, step by step ------------------------------------------------------------------------------------------------
 // 1. the checks that need no device
 int validate_config(const ksa_config* cfg) {
@@ -855,9 +910,18 @@ int validate_config(const ksa_config* cfg) {
   for (int i = 0; i < cfg->num_windows; ++i)
     if (cfg->window_starts[i] < 0 || cfg->window_starts[i] + n > cfg->full_size)
       return fail("window %d start %d runs past the block", i, cfg->window_starts[i]);
-  if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_PFB) return fail("unknown cumu_mode %d", cfg->cumu_mode);
+  if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_PFB_PSD) return fail("unknown cumu_mode %d", cfg->cumu_mode);
   if (cfg->cumu_mode == KSA_CUMU_PFB && cfg->num_windows > KSA_PFB_MAX_TAPS)
     return fail("KSA_CUMU_PFB: num_windows %d outside 1..%d taps", cfg->num_windows, KSA_PFB_MAX_TAPS);
+  if (cfg->cumu_mode == KSA_CUMU_PFB_PSD) {
+    if (cfg->num_windows > KSA_PFB_MAX_TAPS)
+      return fail("KSA_CUMU_PFB_PSD: num_windows %d outside 1..%d taps", cfg->num_windows, KSA_PFB_MAX_TAPS);
+    // one block's folded sub-frames must fit a fold + transform chunk
+    const long long bytes = (long long)pfb_subframes(cfg) * n * 8;
+    if (bytes > (long long)KSA_PFB_CHUNK_BYTES)
+      return fail("KSA_CUMU_PFB_PSD: %lld bytes of folded sub-frames per block (%d x fft_size %d x 8) exceed the chunk of %lld bytes",
+                  bytes, pfb_subframes(cfg), n, (long long)KSA_PFB_CHUNK_BYTES);
+  }
   if (mixed && (cfg->hm_width < 0 || (cfg->hm_width && n % cfg->hm_width)))
     return fail("hm_width %d must divide fft_size %d", cfg->hm_width, n);
   if (!mixed && (cfg->hm_width < 0 || (cfg->hm_width && (n % cfg->hm_width || !is_pow2(cfg->hm_width)))))
@@ -874,6 +938,7 @@ int validate_config(const ksa_config* cfg) {
 
 // What the transform stage plans from and runs on: the caller's windows or, on a KSA_CUMU_PFB engine, the inner shape -- one
 // window at start 0 with all-ones taps over a folded frame of N samples (the caller's starts and taps [P][N] belong to the fold).
+// KSA_CUMU_PFB_PSD: K windows at j*N with all-ones taps over a folded frame of K*N samples.
 struct WindowShape {
   int num_windows;
   const int32_t* starts;
@@ -884,12 +949,14 @@ struct WindowShape {
 void choose_plan(ksa_engine* e, const ksa_config* cfg, const WindowShape& w) {
   const int n = cfg->fft_size;
   e->win_ones = std::all_of(w.taps, w.taps + n, [](float t) { return t == 1.0f; });
-  if (fold_pfb(e)) {
+  if (fold_time(e)) {
     const int p = cfg->num_windows;
     e->pfb_ring_ok = p == 4 || p == 8 || p == 16;
     for (int k = 0; k < p; ++k) e->pfb_ring_ok &= (long long)cfg->window_starts[k] == (long long)k * n;
-    // whole frames, a multiple of 4 (even for the pair kernel, 16-byte aligned waterfall row offsets), at least 4
-    const long long chunk = std::max<long long>(4, (long long)KSA_PFB_CHUNK_BYTES / ((long long)n * 8) / 4 * 4);
+    e->pfb_sub = fold_pfb_psd(e) ? w.num_windows : 1;
+    // whole frames (KSA_CUMU_PFB_PSD: whole blocks of K sub-frames), a multiple of 4 (even for the pair kernel, 16-byte aligned
+    // waterfall row offsets), at least 4
+    const long long chunk = std::max<long long>(4, (long long)KSA_PFB_CHUNK_BYTES / ((long long)e->pfb_sub * n * 8) / 4 * 4);
     e->pfb_chunk = (int)std::min<long long>(chunk, ((long long)cfg->max_frames + 3) / 4 * 4);
   }
   if (is_mixed_radix(n)) {
@@ -924,7 +991,7 @@ int upload(T** dst, const std::vector<T>& src) { return upload(dst, src.data(), 
 int upload_tables(ksa_engine* e, const ksa_config* cfg, const WindowShape& w) {
   namespace tab = ksa::tables;
   const int n = cfg->fft_size, sn = e->sub_n;
-  if (fold_pfb(e)) {
+  if (fold_time(e)) {
     if (upload(&e->d_pfb_starts, cfg->window_starts, (size_t)cfg->num_windows)) return 1;
     if (upload(&e->d_pfb_taps, cfg->window, (size_t)cfg->num_windows * n)) return 1;
   }
@@ -972,8 +1039,9 @@ int alloc_scratch(ksa_engine* e, int num_windows) {
   const int n = c.fft_size;
   const size_t nn = (size_t)n;
   hipError_t he;
-  if (fold_pfb(e) && (he = hipMalloc(reinterpret_cast<void**>(&e->d_pfb_y), (size_t)e->pfb_chunk * n * sizeof(float2))) != hipSuccess)
-    return fail("hipMalloc(%zu) for the folded frames: %s", (size_t)e->pfb_chunk * n * sizeof(float2), hipGetErrorString(he));
+  const size_t folded = (size_t)e->pfb_chunk * e->pfb_sub * n * sizeof(float2);
+  if (fold_time(e) && (he = hipMalloc(reinterpret_cast<void**>(&e->d_pfb_y), folded)) != hipSuccess)
+    return fail("hipMalloc(%zu) for the folded frames: %s", folded, hipGetErrorString(he));
   if (e->path == 2) {
     const int n1 = e->sub_n, nw = num_windows;
     // scratch: Z = 8 N bytes per window.  Chunks of <= KSA_FS_SCRATCH_MB (default below) of Z
@@ -1038,10 +1106,12 @@ int ksa_create(const ksa_config* cfg, ksa_engine** out) {
   e->num_cu = prop.multiProcessorCount;
   auto bail = [&](int r) { ksa_destroy(e); return r; };
 
-  const bool pfb = fold_pfb(e);
+  const bool pfb = fold_time(e);
   const std::vector<float> pfb_ones(pfb ? (size_t)cfg->fft_size : 0, 1.0f);
-  const int32_t pfb_start0 = 0;
-  const WindowShape w = pfb ? WindowShape{1, &pfb_start0, pfb_ones.data()} : WindowShape{cfg->num_windows, cfg->window_starts, cfg->window};
+  std::vector<int32_t> pfb_inner(fold_pfb_psd(e) ? (size_t)pfb_subframes(cfg) : 1);      // j*N (one window at 0 on a KSA_CUMU_PFB engine)
+  for (size_t j = 0; j < pfb_inner.size(); ++j) pfb_inner[j] = (int32_t)j * cfg->fft_size;
+  const WindowShape w = pfb ? WindowShape{(int)pfb_inner.size(), pfb_inner.data(), pfb_ones.data()}
+                            : WindowShape{cfg->num_windows, cfg->window_starts, cfg->window};
   choose_plan(e, cfg, w);
   if (upload_tables(e, cfg, w)) return bail(1);
   if (configure_kernels(e, w.num_windows)) return bail(1);

@@ -11,6 +11,14 @@
 //                             load per output point, P-1 warm-up loads per slice.  The frame loop is unrolled by P, which makes
 //                             every ring index a compile-time constant (no scratch).
 // A thread owns PFB_COLS adjacent columns: one 16-byte store per frame, one 16 / 8 / 4-byte load per segment.
+//
+// Integrating polyphase spectrometer (KSA_CUMU_PFB_PSD): a block holds K sub-frames that advance by N samples,
+//   y[b*K + j][n] = sum over k < P of x[b*frame_stride + j*N + starts[k] + n] * taps[k*N + n]            j = 0 .. K-1
+// written as complex64 [blocks*K][N]; the transform stage then runs its PSD instantiations over every block as ONE frame of K
+// rectangular windows at hop N.  The same arithmetic in two block-aware kernels:
+//   pfbpsd_fold_kernel<FMT>      any starts, any stride, any P.
+//   pfbpsd_ring_kernel<FMT, P>   starts[k] == k*N and pfbpsd_ring_pays(FMT, P) (P = 4, 8, 16): the sliding happens INSIDE a block, whatever
+//                                frame_stride is; a thread walks one slice of at most PFB_SLICE_FRAMES sub-frames of one block.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,6 +130,73 @@ __global__ __launch_bounds__(PFB_THREADS) void pfb_ring_kernel(const PfbParams a
 #pragma unroll
         for (int k = 0; k < P; ++k) acc = pfb_mac(acc, ring[(u + k) % P], w[k]);
         *reinterpret_cast<pfb_f4*>(a.y + (size_t)(f + u) * a.n + col) = acc;
+      }
+    }
+  }
+}
+
+// ---- KSA_CUMU_PFB_PSD: K sub-frames per block -------------------------------------------------------------------------------
+// Where the block ring kernel ships: where it measured faster than the block generic kernel (profiles/pfbpsd_sweep.txt) -- every
+// sample format at P = 4, 8, 16, the 2-byte formats at P = 4 included (1.70 x there, where pfb_ring_pays keeps the frame-wise
+// ring kernel out: inside a block the ring form also spares the generic form's per-item index arithmetic, and it won down to
+// K = 1, where both load the same samples).  Only these pairs are instantiated.
+__host__ __device__ constexpr bool pfbpsd_ring_pays(int fmt, int taps) {
+  return fmt >= FMT_C64 && fmt <= FMT_S16 && (taps == 4 || taps == 8 || taps == 16);
+}
+
+struct PfbPsdParams {
+  PfbParams f;   // iq, frame_stride (between BLOCKS), nframes = blocks, n, ntaps, starts, taps, u8_*, y = [blocks*nsub][N]
+  int nsub;      // K: sub-frames per block
+};
+
+// One work item = PFB_COLS adjacent columns of one (block, sub-frame), numbered row-major over [blocks*K][N / PFB_COLS] and
+// walked in grid strides: a wave reads adjacent columns.
+template <int FMT>
+__global__ __launch_bounds__(PFB_THREADS) void pfbpsd_fold_kernel(const PfbPsdParams a) {
+  const int per = a.f.n / PFB_COLS;
+  const long long items = (long long)a.f.nframes * a.nsub * per;
+  for (long long i = (long long)blockIdx.x * PFB_THREADS + threadIdx.x; i < items; i += (long long)gridDim.x * PFB_THREADS) {
+    const int row = (int)(i / per), col = (int)(i - (long long)row * per) * PFB_COLS;
+    const int b = row / a.nsub, j = row - b * a.nsub;
+    const long long base = (long long)b * a.f.frame_stride + (long long)j * a.f.n + col;
+    pfb_f4 acc = pfb_f4{0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < a.f.ntaps; ++k) {
+      const float2 w = *reinterpret_cast<const float2*>(a.f.taps + (size_t)k * a.f.n + col);
+      acc = pfb_mac(acc, pfb_sample<FMT>(a.f, base + a.f.starts[k]), w);
+    }
+    *reinterpret_cast<pfb_f4*>(a.f.y + (size_t)row * a.f.n + col) = acc;
+  }
+}
+
+// One work item = PFB_COLS adjacent columns of one slice of at most PFB_SLICE_FRAMES sub-frames of one block, numbered
+// (block, slice)-major; one item per thread.  Segment s of block b = samples [b*frame_stride + s*N, ... + N); sub-frame j folds
+// segments j .. j+P-1.  K need be no multiple of P or of the slice: the unrolled trip is guarded per sub-frame.
+template <int FMT, int P>
+__global__ __launch_bounds__(PFB_THREADS) void pfbpsd_ring_kernel(const PfbPsdParams a) {
+  const int per = a.f.n / PFB_COLS;
+  const int slices = (a.nsub + PFB_SLICE_FRAMES - 1) / PFB_SLICE_FRAMES;
+  const long long i = (long long)blockIdx.x * PFB_THREADS + threadIdx.x;
+  const int bs = (int)(i / per), col = (int)(i - (long long)bs * per) * PFB_COLS;
+  const int b = bs / slices, slice = bs - b * slices;
+  if (b >= a.f.nframes) return;
+  const int f0 = slice * PFB_SLICE_FRAMES, f1 = min(f0 + PFB_SLICE_FRAMES, a.nsub);
+  const long long x0 = (long long)b * a.f.frame_stride + col;     // the block's segment 0, this thread's columns
+  float2* const y = a.f.y + ((size_t)b * a.nsub) * a.f.n + col;
+  float2 w[P];
+#pragma unroll
+  for (int k = 0; k < P; ++k) w[k] = *reinterpret_cast<const float2*>(a.f.taps + (size_t)k * a.f.n + col);
+  pfb_f4 ring[P];     // segment f0 + j lives in ring[j % P]
+#pragma unroll
+  for (int j = 0; j < P - 1; ++j) ring[j] = pfb_sample<FMT>(a.f, x0 + (long long)(f0 + j) * a.f.n);
+  for (int f = f0; f < f1; f += P) {
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      if (f + u < f1) {
+        ring[(u + P - 1) % P] = pfb_sample<FMT>(a.f, x0 + (long long)(f + u + P - 1) * a.f.n);
+        pfb_f4 acc = pfb_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < P; ++k) acc = pfb_mac(acc, ring[(u + k) % P], w[k]);
+        *reinterpret_cast<pfb_f4*>(y + (size_t)(f + u) * a.f.n) = acc;
       }
     }
   }

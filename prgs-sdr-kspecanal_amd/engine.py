@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import lib, check, Config, CUMU, CUMU_PFB, PFB_MAX_TAPS, FMT_C64, FMT_U8, FMT_S8, FMT_S16, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS, KsaError
+from ._lib import lib, check, Config, CUMU, CUMU_PFB, CUMU_PFB_PSD, PFB_MAX_TAPS, FMT_C64, FMT_U8, FMT_S8, FMT_S16, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS, KsaError
 
 MIN_AMP_DEFAULT = (1 / 256) * 0.00001   # gMinAmp4Clip K:53
 FFT2FULL_LESS, FFT2FULL_MORE = 8, 2     # K:49-50
@@ -152,24 +152,36 @@ class SpectrumEngine:
     def __init__(self, fft_size, full_size=None, sampling_rate=2.4e6, non_overlap=0.1, window="ones",
                  cumu_mode="AVG", gain=19.1, min_amp=MIN_AMP_DEFAULT, xres=512, max_frames=1, device=0,
                  scan_total_entries=0, scan_non_overlap=0.5, scan_xres=None,
-                 u8_offset=127.5, u8_scale=127.5, stream=None, psd_fs=2.0, pfb_taps=0):
+                 u8_offset=127.5, u8_scale=127.5, stream=None, psd_fs=2.0, pfb_taps=0, pfb_spectra=0):
         """pfb_taps = P >= 1 turns the polyphase front end on (KSA_CUMU_PFB): every block is P segments of fftSize samples at
         k*fftSize, weighted by the prototype `window` -- a name (pfb_window(fftSize, P, name)) or an array of P*fftSize
         taps --, summed and transformed once; full_size defaults to P*fftSize, mag_scale = 2 / sum(taps) (K:373 / K:391 read
-        on the long window: a unit tone reads 2.0), cumu_mode stays at its default and non_overlap is unused."""
+        on the long window: a unit tone reads 2.0), cumu_mode stays at its default and non_overlap is unused.
+        pfb_spectra = K >= 1 (needs pfb_taps) makes it the integrating polyphase spectrometer (KSA_CUMU_PFB_PSD): a block holds K
+        sub-frames that advance by fftSize samples, each folded as above, and the engine returns the sum of their K power
+        spectra; full_size defaults to (P+K-1)*fftSize and mag_scale = 1 / (psd_fs * sum(taps^2) * K), a density as under
+        cumu_mode PSD (unit-variance white noise reads 1/psd_fs)."""
         self.fft_size = int(fft_size)
         if not fft_size_supported(self.fft_size):
             raise KsaError(fft_size_message(self.fft_size))
         self.pfb_taps = int(pfb_taps)
         if self.pfb_taps and not 1 <= self.pfb_taps <= PFB_MAX_TAPS:
             raise KsaError("pfb_taps %d outside 1..%d" % (self.pfb_taps, PFB_MAX_TAPS))
+        self.pfb_spectra = int(pfb_spectra)
+        if self.pfb_spectra < 0:
+            raise KsaError("pfb_spectra %d must be 0 (off) or >= 1" % self.pfb_spectra)
+        if self.pfb_spectra and not self.pfb_taps:
+            raise KsaError("pfb_spectra %d needs pfb_taps >= 1" % self.pfb_spectra)
         if self.pfb_taps and cumu_mode.upper() != "AVG":
             raise KsaError("pfb_taps replaces the within-block fold: cumu_mode [%s] cannot be combined with it" % cumu_mode)
         if self.pfb_taps and full_size is None:
-            full_size = self.pfb_taps * self.fft_size
+            full_size = (self.pfb_taps + max(1, self.pfb_spectra) - 1) * self.fft_size
         self.full_size = int(full_size) if full_size is not None else full_size_for(self.fft_size, sampling_rate)
         if self.pfb_taps and self.full_size < self.pfb_taps * self.fft_size:
             raise KsaError("fullSize %d holds fewer than pfb_taps %d segments of fftSize %d" % (self.full_size, self.pfb_taps, self.fft_size))
+        if self.pfb_spectra and self.full_size // self.fft_size - self.pfb_taps + 1 != self.pfb_spectra:
+            raise KsaError("fullSize %d holds %d spectra of pfb_taps %d x fftSize %d, pfb_spectra is %d" % (
+                self.full_size, self.full_size // self.fft_size - self.pfb_taps + 1, self.pfb_taps, self.fft_size, self.pfb_spectra))
         self.non_overlap = float(non_overlap)
         self.cumu_mode = cumu_mode.upper()
         if self.cumu_mode not in CUMU:
@@ -190,6 +202,9 @@ class SpectrumEngine:
         if self.pfb_taps:
             self.starts = np.arange(self.pfb_taps, dtype=np.int32) * np.int32(self.fft_size)
             self.mag_scale = 2.0 / float(np.sum(win))
+            if self.pfb_spectra:       # a power density, as under cumu_mode PSD
+                self.psd_fs = float(psd_fs)
+                self.mag_scale = psd_mag_scale(win, self.pfb_spectra, self.psd_fs)
         elif self.cumu_mode == "PSD":      # Welch PSD: matplotlib's segments and scale instead of K:386 / K:391
             self.psd_fs = float(psd_fs)
             self.starts = psd_window_starts(self.full_size, self.fft_size, self.non_overlap)
@@ -217,7 +232,7 @@ class SpectrumEngine:
             window_starts=self._starts32.ctypes.data_as(C.POINTER(C.c_int32)),
             window=self._win32.ctypes.data_as(C.POINTER(C.c_float)),
             mag_scale=self.mag_scale,
-            cumu_mode=CUMU_PFB if self.pfb_taps else CUMU[self.cumu_mode], gain=self.gain, min_amp=self.min_amp, hm_width=self.hm_width,
+            cumu_mode=CUMU_PFB_PSD if self.pfb_spectra else CUMU_PFB if self.pfb_taps else CUMU[self.cumu_mode], gain=self.gain, min_amp=self.min_amp, hm_width=self.hm_width,
             max_frames=self.max_frames, u8_offset=u8_offset, u8_scale=u8_scale,
             scan_total_entries=self.scan_total, scan_hop=self.scan_hop, scan_hm_width=self.scan_hm_width)
         h = C.c_void_p()

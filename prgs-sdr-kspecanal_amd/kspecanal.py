@@ -12,7 +12,9 @@ arrays handed to matplotlib: d['Fft.Cur'|'Fft.Max'|'Fft.Min'|'Fft.Avg'], the fre
 [128, W] waterfall buffer (K:470-481, K:729).  New keys are additive: `source` (rtlsdr|synth|file:<path>),
 `device`, `iqFormat` (c64|u8|s8|s16), `frameBatch` (zeroSpan blocks per device call, default 1), `pfbTaps` (P >= 1: the
 polyphase filter bank front end -- P*fftSize samples per spectrum, weighted by a sinc prototype tapered with `window`, folded
-onto fftSize points and transformed once; default 0 = off).  What moved to the GPU:
+onto fftSize points and transformed once; default 0 = off), `pfbSpectra` (K >= 1, with pfbTaps: the integrating polyphase
+spectrometer -- a block of (P+K-1)*fftSize samples holds K such spectra, summed as power, a density; default 0 = off).
+What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
 refreshed once per pass (the whole pass is one device call) instead of once per tuned band, and in zeroSpan with
@@ -61,7 +63,7 @@ _KEYS = {
     "ZEROSPANSAVEFILE": ("zeroSpanSaveFile", str), "ZEROSPANPLAYFILE": ("zeroSpanPlayFile", str),
     # additive keys of this build
     "SOURCE": ("source", str), "DEVICE": ("device", int), "IQFORMAT": ("iqFormat", str.lower),
-    "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int),
+    "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int), "PFBSPECTRA": ("pfbSpectra", int),
 }
 
 
@@ -76,7 +78,7 @@ def defaults():
         "SaveSigLvls": "", "AdjSigLvls": "", "bDataMin": True, "bDataMax": True, "bDataAvg": True, "bDataCur": True,
         "bGrid": True, "bUsePSD": False, "bScanRangeBaseDataIsRaw": False,
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
-        "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "cmd.stop": False,
+        "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
     }
 
 
@@ -162,8 +164,16 @@ def handle_args(d, argv=None):
 
 def _handle_pfb(d):
     """pfbTaps P (additive): the polyphase front end.  fullSize becomes P*fftSize (P segments of fftSize samples per
-    spectrum), `window` names the taper of the prototype; the within-block overlap and fold have nothing left to do."""
-    taps = d["pfbTaps"]
+    spectrum), `window` names the taper of the prototype; the within-block overlap and fold have nothing left to do.
+    pfbSpectra K (additive, needs pfbTaps): the integrating polyphase spectrometer, fullSize (P+K-1)*fftSize."""
+    taps, spectra = d["pfbTaps"], d["pfbSpectra"]
+    if spectra < 0:
+        prg_quit(d, "ERROR:handle_args: pfbSpectra [{}] must be 0 (off) or >= 1".format(spectra))
+    if spectra and d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: pfbSpectra [{}] is ignored when playing saved spectra".format(spectra))
+        d["pfbSpectra"] = spectra = 0
+    if spectra and (taps < 1 or taps > _engine.PFB_MAX_TAPS):
+        prg_quit(d, "ERROR:handle_args: pfbSpectra [{}] needs pfbTaps 1..{}".format(spectra, _engine.PFB_MAX_TAPS))
     if taps < 0 or taps > _engine.PFB_MAX_TAPS:
         prg_quit(d, "ERROR:handle_args: pfbTaps [{}] must be 0 (off) or 1..{}".format(taps, _engine.PFB_MAX_TAPS))
     if taps == 0:
@@ -180,7 +190,7 @@ def _handle_pfb(d):
     if d["curScanNonOverlap"] != dflt["curScanNonOverlap"] or d["curScanCumuMode"] != dflt["curScanCumuMode"]:
         print("WARN:handle_args: curScanNonOverlap [{}] and curScanCumuMode [{}] are unused with pfbTaps [{}]".format(
             d["curScanNonOverlap"], d["curScanCumuMode"], taps))
-    d["fullSize"] = taps * d["fftSize"]
+    d["fullSize"] = (taps + max(1, spectra) - 1) * d["fftSize"]
 
 
 def print_info(d):
@@ -197,7 +207,10 @@ def print_info(d):
         d["xRes"], d["bGrid"], d["pltCompress"], d["pltCompressHM"]))
     print("INFO: source [{}], device [{}], iqFormat [{}], frameBatch [{}]".format(d["source"], d["device"], d["iqFormat"],
                                                                                 d["frameBatch"]))
-    if d["pfbTaps"]:
+    if d["pfbTaps"] and d.get("pfbSpectra"):
+        print("INFO: pfbTaps [{}] pfbSpectra [{}]: fullSize[{}] = (pfbTaps + pfbSpectra - 1) x fftSize, power, density; prototype sinc x window[{}]".format(
+            d["pfbTaps"], d["pfbSpectra"], d["fullSize"], d["window"]))
+    elif d["pfbTaps"]:
         print("INFO: pfbTaps [{}]: fullSize[{}] = pfbTaps x fftSize, prototype sinc x window[{}]".format(
             d["pfbTaps"], d["fullSize"], d["window"]))
 
@@ -302,12 +315,12 @@ def sdr_read(sdr, length, raw=False):
 def get_engine(d, scan_total=0, max_frames=1):
     """One engine per (geometry, mode) -- rebuilt when a GUI toggle or argument changes the key."""
     key = (d["fftSize"], d["fullSize"], d["curScanNonOverlap"], d["curScanCumuMode"], d["window"], d["gain"],
-           d["minAmp4Clip"], d["xRes"], scan_total, d["scanRangeNonOverlap"], max_frames, d["device"], d.get("pfbTaps", 0))
+           d["minAmp4Clip"], d["xRes"], scan_total, d["scanRangeNonOverlap"], max_frames, d["device"], d.get("pfbTaps", 0), d.get("pfbSpectra", 0))
     if d.get("ksa.key") != key:
         if d.get("ksa.engine") is not None:
             d["ksa.engine"].close()
         if d.get("pfbTaps", 0):      # the polyphase front end: `window` names the prototype's taper, the fold is the engine's
-            shape = dict(window=d["window"], pfb_taps=d["pfbTaps"])
+            shape = dict(window=d["window"], pfb_taps=d["pfbTaps"], pfb_spectra=d.get("pfbSpectra", 0))
         else:
             shape = dict(window=d["theWin"], cumu_mode=d["curScanCumuMode"])
         d["ksa.engine"] = SpectrumEngine(
