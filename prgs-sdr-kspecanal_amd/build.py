@@ -1,5 +1,7 @@
 """Build libksa.so (HIP kernels + C ABI) for gfx950 with hipcc.  In-tree, no JIT cache:
-the .so sits next to this file so that it travels to the GPU box with the repo snapshot."""
+the .so sits next to this file so that it travels to the GPU box with the repo snapshot.
+Beside it libksa_exp.so, the same sources with -DKSA_EXPERIMENTS: the only build that reads the KSA_* environment
+switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel through it); the package never loads it."""
 import os
 import shutil
 import subprocess
@@ -8,6 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "ksa_api.hip")
 OUT = os.path.join(HERE, "libksa.so")
+OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
@@ -17,25 +20,33 @@ def sources():
     return [os.path.join(d, f) for f in sorted(os.listdir(d))] + [os.path.join(HERE, "..", "include", "ksa.h")]
 
 
-def is_stale():
-    if not os.path.exists(OUT):
+def is_stale(out=OUT):
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
+    t = os.path.getmtime(out)
     return any(os.path.getmtime(s) > t for s in sources())
 
 
 def build(force=False, verbose=False):
-    """Compile if the library is missing or older than its sources.  Returns the .so path."""
-    if not force and not is_stale():
-        return OUT
+    """Compile what is missing or older than its sources (the two libraries side by side).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc] + FLAGS + ["-o", OUT + ".tmp", SRC]
-    if verbose:
-        print(" ".join(cmd))
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)
-    os.replace(OUT + ".tmp", OUT)
+    jobs = []
+    for out, extra in ((OUT, []), (OUT_EXP, ["-DKSA_EXPERIMENTS"])):
+        if not force and not is_stale(out):
+            continue
+        cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", SRC]
+        if verbose:
+            print(" ".join(cmd))
+        jobs.append((out, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+    failed = []
+    for out, proc in jobs:
+        log = proc.communicate()[0]
+        if proc.returncode != 0:
+            failed.append(log)
+        else:
+            os.replace(out + ".tmp", out)
+    if failed:
+        raise RuntimeError("hipcc failed:\n" + "\n".join(failed))
     return OUT
 
 

@@ -116,6 +116,7 @@ struct ksa_engine {
   float* d_levels = nullptr;      // [4][cells] plot-side decimation scratch
   int* d_highs = nullptr;         // peak markers: [HIGHS_MAX] cell | [HIGHS_MAX] level (float bits) | found
   float* d_parts = nullptr;       // [capacity][N] partial folds of the window-split (latency) mode
+  unsigned* d_tickets = nullptr;  // the unit counter of spectrum_kernel's ticket walk: this engine's alone, zeroed on its stream before every launch
   int levels_cap = 0;
   // multi-engine merges inside one process (ksa_allreduce_state, ksa_scan_allstitch) and the host-pointer scan pass
   float* d_gather = nullptr;      // [n][4N + 128W] every engine's exchange block, or [n][rows][scan_hm_width]
@@ -291,8 +292,14 @@ int configure_kernel(K kfn, int threads, int lds_bytes, KernelFit* fit, int lds_
 // `may_split`: every frame's windows are split over several workgroups so that the GPU is filled, and the partial folds are
 // combined by a second, tiny kernel (pays from N = 1024 up: 84 -> 51 us per block at N=4096, 720 -> 117 us at N=16384; tiny
 // transforms only lose the launches).  `grid_cap` bounds the grid (measurements; INT_MAX otherwise).
+// `tickets` (spectrum_kernel at one transform per workgroup): units are handed out on demand through the engine's counter, which is
+// zeroed on the stream in front of the launch (launches of one engine are stream-ordered: one counter serves them all).  Only
+// where a unit is long enough that the draws stay rare -- one atomic per unit on one address: a unit of TICKET_MIN_POINTS
+// window points is some 20 us of a workgroup (4 us per 4096-point window at three workgroups per CU); shorter units (RAW mode,
+// few windows at N = 1024, thin window-split shares) keep the static walk, as do the kernels of several transforms per workgroup.
+constexpr long long TICKET_MIN_POINTS = 5 * 4096;
 template <class K>
-int launch_split(ksa_engine* e, K kfn, const SpecParams& p, int n, int threads, int lds_bytes, bool may_split, int grid_cap) {
+int launch_split(ksa_engine* e, K kfn, const SpecParams& p, int n, int threads, int lds_bytes, bool may_split, int grid_cap, bool tickets = false) {
   const int capacity = e->num_cu * e->blocks_per_cu;
   SpecParams q = p;
   const int plan = plan_of(e, p);
@@ -302,6 +309,10 @@ int launch_split(ksa_engine* e, K kfn, const SpecParams& p, int n, int threads, 
   }
   int grid = std::max(1, std::min(q.nframes * std::max(1, q.parts), capacity));
   grid = std::max(1, std::min(grid, grid_cap));
+  if (tickets && e->d_tickets && !exp_env("KSA_STATIC_WALK") && (long long)(p.nwin / std::max(1, q.parts)) * n >= TICKET_MIN_POINTS) {
+    HIP_OK(hipMemsetAsync(e->d_tickets, 0, sizeof(unsigned), e->stream));
+    q.tickets = e->d_tickets;
+  }
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), lds_bytes, e->stream, q);
   if (q.parts > 1) {
     hipLaunchKernelGGL(ksa::combine_parts_kernel, dim3((n / 4 + 63) / 64, q.nframes), dim3(64), 0, e->stream, q, n);
@@ -310,6 +321,23 @@ int launch_split(ksa_engine* e, K kfn, const SpecParams& p, int n, int threads, 
   }
   HIP_OK(hipGetLastError());
   return 0;
+}
+
+// The same walk for spectrum64_kernel / spectrum_pair_kernel (`units` frames / pairs of `points` window points each, at most `cap`
+// workgroups): their units are short, so a ticket covers a run of consecutive units that holds >= TICKET_MIN_POINTS points, and only
+// batches in which every workgroup draws at least two runs take it -- smaller ones keep the stride walk and the grid they had.
+// Sets q.tickets / q.ticket_run (zeroing the counter on the stream) and returns the grid; < 0 on a HIP error.
+int ticket_runs(ksa_engine* e, SpecParams& q, int units, long long points, int cap) {
+  if (const char* g = exp_env("KSA_GRID")) cap = std::max(1, std::min(cap, atoi(g)));
+  const int run = (int)std::max<long long>(1, (TICKET_MIN_POINTS + points - 1) / std::max<long long>(1, points));
+  q.ticket_run = 1;
+  if (e->d_tickets && !exp_env("KSA_STATIC_WALK") && units >= 2ll * cap * run) {
+    if (hipMemsetAsync(e->d_tickets, 0, sizeof(unsigned), e->stream) != hipSuccess) return -1;
+    q.tickets = e->d_tickets;
+    q.ticket_run = run;
+    return cap;
+  }
+  return std::max(1, std::min(units, cap));
 }
 
 template <int N, int FMT, int RM, int CM>
@@ -327,8 +355,10 @@ int launch_pair_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
     return 0;
   }
   const int npairs = (p.nframes + 1) / 2;
-  const int grid = std::max(1, std::min(npairs, e->num_cu * e->pair_bpc));
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(ksa::Plan<N>::T), PP::LDS_BYTES, e->stream, p);
+  SpecParams q = p;
+  const int grid = ticket_runs(e, q, npairs, 2ll * p.nwin * N, e->num_cu * e->pair_bpc);
+  if (grid < 0) return fail("hipMemsetAsync of the ticket counter failed");
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(ksa::Plan<N>::T), PP::LDS_BYTES, e->stream, q);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -355,7 +385,8 @@ int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
     }
     return 0;
   }
-  return launch_split(e, kfn, p, N, P::T, lds_bytes, N >= 1024, INT_MAX);
+  const char* g = exp_env("KSA_GRID");   // measurement: fewer persistent workgroups
+  return launch_split(e, kfn, p, N, P::T, lds_bytes, N >= 1024, g ? atoi(g) : INT_MAX, P::S == 1);
 }
 
 template <int N, int FMT, int RM>
@@ -438,8 +469,10 @@ int launch_spec64_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
     }
     return 0;
   }
-  const int grid = std::max(1, std::min(p.nframes, e->num_cu * e->k64_bpc));
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(ksa::Plan64::T), ksa::Plan64::LDS_BYTES, e->stream, p);
+  SpecParams q = p;
+  const int grid = ticket_runs(e, q, p.nframes, (long long)p.nwin * ksa::Plan64::N, e->num_cu * e->k64_bpc);
+  if (grid < 0) return fail("hipMemsetAsync of the ticket counter failed");
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(ksa::Plan64::T), ksa::Plan64::LDS_BYTES, e->stream, q);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -662,6 +695,7 @@ int run_dif16(ksa_engine* e, const SpecParams& p, int fmt, int batch_first, int 
     b.cumu = p.cumu;
     b.out_mode = ksa::OUT_LINEAR;
     b.out = e->d_dif_y;
+    b.dbg = p.dbg;                 // (diagnostic builds: the second stage's records; null otherwise)
     e->plan_frames = chunk_frames * R;
     if (launch_spec_n<ksa::FMT_C64>(e, b, false)) return 1;
     ksa::DifFinishParams c{};
@@ -741,11 +775,11 @@ int run_transform(ksa_engine* e, const Frames& f, int out_mode, float* out, bool
   p.hm_index0 = (e->hm_index + f.batch_first) % KSA_HM_ROWS;
   p.hm_first = std::max(0, f.batch_frames - KSA_HM_ROWS - f.batch_first);
   e->plan_frames = f.batch_frames;
-#ifdef KSA_STAMPS
-  static unsigned long long* dbg = nullptr;   // diagnostic build: 4096 blocks x 16 waves x 12 segments
-  const size_t dbg_n = 4096 * 16 * 12;
-  if (!dbg) hipMalloc(reinterpret_cast<void**>(&dbg), dbg_n * 8);
-  hipMemsetAsync(dbg, 0, dbg_n * 8, e->stream);
+#ifdef KSA_SKEW
+  static unsigned long long* dbg = nullptr;   // diagnostic build: 4096 blocks x 16 waves x 12 segments, then 4096 workgroup records
+  const size_t dbg_n = ksa::SKEW_SEG_WORDS, skew_n = (size_t)ksa::SKEW_WGS * 4;
+  if (!dbg) hipMalloc(reinterpret_cast<void**>(&dbg), (dbg_n + skew_n) * 8);
+  hipMemsetAsync(dbg, 0, (dbg_n + skew_n) * 8, e->stream);
   p.dbg = dbg;
 #endif
   // profiled stage: clock stamps directly before and after it on the same stream (ksa_prof_clock), OUTSIDE the event pair
@@ -782,6 +816,23 @@ int run_transform(ksa_engine* e, const Frames& f, int out_mode, float* out, bool
 #endif
   if (prof_end(e, ea, eb)) return 1;
   if (clk) hipLaunchKernelGGL(ksa::clock_stamp_kernel, dim3(ksa::CLK_WGS), dim3(64), 0, e->stream, clk, 1);
+#ifdef KSA_SKEW
+  // one line per workgroup of this call's (last) spectrum launch: "launch <k> <wg> <xcc> <start> <end> <units>", wall clock in
+  // 100 MHz ticks; tools/ticket_skew.py turns them into first / median / last finish per XCD
+  if (const char* path = getenv("KSA_SKEW_FILE")) {
+    static int skew_launch = 0;
+    hipStreamSynchronize(e->stream);
+    std::vector<unsigned long long> h(skew_n);
+    hipMemcpy(h.data(), dbg + dbg_n, skew_n * 8, hipMemcpyDeviceToHost);
+    if (FILE* fp = fopen(path, "a")) {
+      for (int w = 0; w < ksa::SKEW_WGS; ++w)
+        if (h[w * 4 + 1])
+          fprintf(fp, "launch %d %d %llu %llu %llu %llu\n", skew_launch, w, h[w * 4 + 3], h[w * 4 + 0], h[w * 4 + 1], h[w * 4 + 2]);
+      fclose(fp);
+    }
+    ++skew_launch;
+  }
+#endif
   return 0;
 }
 
@@ -1072,6 +1123,7 @@ int alloc_scratch(ksa_engine* e, int num_windows) {
   if (c.hm_width) e->d_hm = e->d_xchg + 4 * nn;
   ALLOC(e->d_state, 4 * nn * 4);
   if (e->path != 6) ALLOC(e->d_parts, (size_t)e->num_cu * e->blocks_per_cu * (size_t)e->sub_n * 4);   // (path 6 has no window split)
+  ALLOC(e->d_tickets, sizeof(unsigned));
   if (c.scan_total_entries) {
     ALLOC(e->d_scan_state, (size_t)4 * c.scan_total_entries * 4);
     ALLOC(e->d_scan_hm, (size_t)KSA_HM_ROWS * c.scan_hm_width * 4);
@@ -1136,7 +1188,7 @@ void ksa_destroy(ksa_engine* e) {
   void* ptrs[] = {e->d_slot[0], e->d_slot[1], e->d_host_rows, e->d_clk, e->d_gather, e->d_scan_stage, e->d_scan_rows, e->d_scan_halo, e->d_scan_send,
                   e->d_starts, e->d_start_last, e->d_window, e->d_window32, e->d_tw_mid, e->d_tw_last, e->d_adj, e->d_scan_adj,
                   e->d_iq_stage, e->d_frames, e->d_part, e->d_xchg, e->d_state, e->d_scan_state, e->d_scan_hm,
-                  e->d_levels, e->d_parts, e->d_highs, e->d_scan_avg_rows, e->d_dif_tw, e->d_dif_z, e->d_dif_y, e->d_ones, e->d_starts_b,
+                  e->d_levels, e->d_parts, e->d_tickets, e->d_highs, e->d_scan_avg_rows, e->d_dif_tw, e->d_dif_z, e->d_dif_y, e->d_ones, e->d_starts_b,
                   e->d_pfb_starts, e->d_pfb_taps, e->d_pfb_y};
   for (void* p : ptrs) if (p) hipFree(p);
   delete e;

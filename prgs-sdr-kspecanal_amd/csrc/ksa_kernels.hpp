@@ -2,7 +2,8 @@
 //
 //  spectrum_kernel<N,FMT>   rows A0,A4-A9,A12 of SURVEY.md section 8: unpack, window, FFT, |X|,
 //                           fold over the block's windows, fftshift, dB, waterfall row.
-//                           One workgroup walks frames (persistent, grid-stride); the transform
+//                           One workgroup walks frames (persistent; frames are handed out by ticket where
+//                           one transform fills the workgroup, by grid stride otherwise); the transform
 //                           lives in VGPRs + LDS, the block of IQ is read from HBM once.
 //  accumulate_*             row A10: Max/Min/Avg/Cur over a batch of frames (K:470-476)
 //  scan_stitch_kernel       row A13: band stitch + per-pass accumulate (K:622-668)
@@ -49,6 +50,9 @@ struct SpecParams {
   int parts;                // > 1: each frame's windows are split over `parts` workgroups (small batches)
   float* part_out;          // [nframes*parts][N] partial folds (natural bin order), combined by combine_parts_kernel
   unsigned long long* dbg;  // diagnostic builds only (-DKSA_STAMPS): [grid][16] cycle sums; null otherwise
+  unsigned* tickets;        // ticket walk of the persistent kernels: the engine's counter, zero at the launch (units are handed out
+                            // on demand); null: the static walk by gridDim.x
+  int ticket_run;           // spectrum64_kernel, spectrum_pair_kernel: consecutive units per ticket (short units); 1 with the static walk
 };
 
 // Shader clock held under the spectrum stage (bench.py `shader_clock_ghz_live`, ksa_prof_clock): a stamp kernel of CLK_WGS
@@ -347,6 +351,45 @@ __device__ __forceinline__ float2 unpack_signed(unsigned b) {
 #else
 #define KSA_STAMP(i) do {} while (0)
 #endif
+// Finish-time skew of the persistent workgroups (diagnostic builds only: -DKSA_SKEW, implied by -DKSA_STAMPS): behind the
+// segment sums p.dbg holds [SKEW_WGS][4] = {wall clock at the workgroup's start, wall clock behind its frame loop, units it
+// transformed, XCC_ID}.  Both stamps sit outside the window loop and are stored at once: nothing of them is live inside it,
+// so a -DKSA_SKEW build times like the shipped kernel (tools/ticket_skew.py reads the records).
+#if defined(KSA_STAMPS) && !defined(KSA_SKEW)
+#define KSA_SKEW 1
+#endif
+constexpr int SKEW_WGS = 4096;
+constexpr size_t SKEW_SEG_WORDS = (size_t)4096 * 16 * 12;   // the segment sums in front of the records
+#ifdef KSA_SKEW
+__device__ __forceinline__ void skew_store(unsigned long long* dbg, int word, unsigned long long v) {
+  if (dbg && threadIdx.x == 0 && blockIdx.x < SKEW_WGS) dbg[SKEW_SEG_WORDS + (size_t)blockIdx.x * 4 + word] = v;
+}
+#define KSA_SKEW_BEGIN() int skew_units = 0; skew_store(p.dbg, 0, wall_clock64())
+#define KSA_SKEW_UNIT() ++skew_units
+#define KSA_SKEW_END()                                                                                      \
+  do {                                                                                                      \
+    skew_store(p.dbg, 1, wall_clock64());                                                                   \
+    skew_store(p.dbg, 2, (unsigned long long)skew_units);                                                   \
+    skew_store(p.dbg, 3, __builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)));   /* HW_REG_XCC_ID */ \
+  } while (0)
+#else
+#define KSA_SKEW_BEGIN() do {} while (0)
+#define KSA_SKEW_UNIT() do {} while (0)
+#define KSA_SKEW_END() do {} while (0)
+#endif
+
+// Ticket walk of the persistent kernels (spectrum_kernel holds the why and the how): lane 0 of the workgroup drew `ticket` from
+// SpecParams::tickets; every wave gets the workgroup's next unit (or run of units) gridDim.x + ticket as a scalar.  Workgroups of
+// several waves pass it through `word` (an LDS word that nothing else uses at that point) and one barrier.
+template <int T>
+__device__ __forceinline__ int ticket_next(unsigned ticket, unsigned* word) {
+  if constexpr (T > 64) {
+    if (threadIdx.x == 0) *word = ticket;
+    __syncthreads();
+    ticket = *word;
+  }
+  return (int)(gridDim.x + (unsigned)__builtin_amdgcn_readfirstlane((int)ticket));
+}
 
 #ifdef KSA_ABL_NOLDS   // timing-only ablation build (no exchange): wrong results by construction
 #define KSA_SYNC() do {} while (0)
@@ -599,7 +642,23 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
   //  them was measured at N = 64, round 5: 168 instead of 121 VGPRs = three instead of four waves per SIMD, config 4 14.9 vs
   //  17.7 G FFT/s (-16 %; uint8 -15 %); held to 128 VGPRs the same code spills 98-110 registers, with the 6-twiddle last pass
   //  as well: profiles/r05_ab_pf0.txt.  Removed.)
-  for (int vf = blockIdx.x; vf < p.nframes * NP; vf += gridDim.x) {
+  // Which units (frames, or (frame, part) in window-split mode) a workgroup transforms.  The three workgroups of a CU do not
+  // run equally fast -- the SIMDs issue oldest wave first, so under an equal split the first workgroup of every CU ends at 64 %
+  // of the launch, the second at 80 %, and the CU finishes its share at two and then one wave per SIMD
+  // (profiles/ticket_skew.txt) -- so units are handed out on demand: the first is blockIdx.x, every later one is
+  // gridDim.x + a ticket drawn from p.tickets (zero at the launch).  The ticket is requested by one lane at the start of the
+  // output stage and consumed behind it (ticket_next: one LDS word, one barrier per unit): nothing of it is live inside the window loop.
+  // The word is the last one of the transform's data region, which the output stage does not touch (its rows fill the front
+  // half) and the next unit stores to only behind its first exchange barrier.  One unit per ticket, so only where a unit is
+  // long (S == 1, and the host hands the counter over only where a unit's windows make the draws rare); a unit's results are a
+  // function of its index alone, whoever computes it.
+  constexpr bool TICKETS = S == 1;
+  static_assert(!TICKETS || NPAD > N, "the ticket word lies behind the output stage's two planes of N floats");
+  const int units = p.nframes * NP;
+  unsigned* const next_unit = reinterpret_cast<unsigned*>(lds + S * NPAD) - 1;
+  KSA_SKEW_BEGIN();
+  for (int vf = blockIdx.x; vf < units;) {
+    KSA_SKEW_UNIT();
     const int frame = vf / NP, part = vf - frame * NP;
     // this workgroup's contiguous share of the frame's windows (contiguous keeps the sample reuse valid)
     const int k_lo = (int)((long long)p.nwin * part / NP), k_hi = (int)((long long)p.nwin * (part + 1) / NP);
@@ -636,6 +695,10 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
     float* const red = reinterpret_cast<float*>(lds);  // [S][N] floats, inside the data region
     __syncthreads();
     KSA_STAMP(9);    // output stage, part 1: the barrier behind the last window (slowest wave, outstanding loads)
+    unsigned ticket = 0;
+    if constexpr (TICKETS) {
+      if (p.tickets && tid == 0) ticket = __hip_atomic_fetch_add(p.tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 #pragma unroll
     for (int i = 0; i < 16; ++i) red[slot * RedStride<N, S>::value + l + L * perm<16>(i)] = acc[i];
     __syncthreads();
@@ -664,7 +727,10 @@ __global__ __launch_bounds__(Plan<N>::T, Tune<N>::WPS) void spectrum_kernel(cons
     }
 #endif
     KSA_STAMP(8);
+    if (TICKETS && p.tickets) vf = ticket_next<T>(ticket, next_unit);
+    else vf += gridDim.x;
   }
+  KSA_SKEW_END();
 #ifdef KSA_STAMPS
   if (p.dbg && (tid & 63) == 0) {
     for (int i = 0; i < 12; ++i) p.dbg[((long long)blockIdx.x * (T / 64) + tid / 64) * 12 + i] = seg[i];

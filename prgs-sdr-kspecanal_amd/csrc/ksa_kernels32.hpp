@@ -186,7 +186,9 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
   unsigned long long t_last;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_last)::"memory");
 #endif
+  KSA_SKEW_BEGIN();   // diagnostic builds only (ksa_kernels.hpp)
   for (int vf = blockIdx.x; vf < total; vf += gridDim.x) {
+    KSA_SKEW_UNIT();
     const int frame = vf / NP;
     const int k_lo = k_lo_of(vf), k_hi = k_hi_of(vf);
     float acc[32];
@@ -326,6 +328,7 @@ __global__ __launch_bounds__(Plan32<N>::T, Plan32<N>::WPS) void spectrum32_kerne
     // (the next frame's first exchange barrier orders these LDS reads before its writes)
     KSA_STAMP(8);        // per-frame output stage
   }
+  KSA_SKEW_END();
 #ifdef KSA_STAMPS
   if (p.dbg && (l & 63) == 0) {
     for (int i = 0; i < 12; ++i) p.dbg[((long long)blockIdx.x * (T / 64) + l / 64) * 12 + i] = seg[i];

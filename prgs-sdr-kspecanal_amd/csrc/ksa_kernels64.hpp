@@ -71,7 +71,14 @@ __global__ __launch_bounds__(64, 4) void spectrum64_kernel(const SpecParams p) {
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_last)::"memory");
 #endif
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  for (int frame = blockIdx.x; frame < p.nframes; frame += gridDim.x) {
+  // Frames in runs of p.ticket_run consecutive ones: a workgroup's first run is blockIdx.x, every later one gridDim.x + a ticket
+  // (the co-resident single-wave workgroups of a CU do not run equally fast: spectrum_kernel, profiles/ticket_skew_others.txt).  A
+  // frame is ~15 us here, hence the runs; the ticket is drawn in the output stage of a run's last frame.  Static walk: runs of one.
+  const int run_len = p.tickets ? p.ticket_run : 1;
+  int run = blockIdx.x, frame = run * run_len, f_hi = min(frame + run_len, p.nframes);
+  KSA_SKEW_BEGIN();   // diagnostic builds only (ksa_kernels.hpp)
+  while (frame < p.nframes) {
+    KSA_SKEW_UNIT();
     float acc[16];
     const float init = p.cumu == CUMU_MIN ? __builtin_inff() : 0.0f;
 #pragma unroll
@@ -163,6 +170,9 @@ __global__ __launch_bounds__(64, 4) void spectrum64_kernel(const SpecParams p) {
     // natural bin order through LDS, then the common output stage: acc[c'*8 + P] is bin (2l + c') + 8*perm8(P)
     float* const red = reinterpret_cast<float*>(lds);
     __syncthreads();
+    const bool run_ends = frame + 1 == f_hi;
+    unsigned ticket = 0;
+    if (p.tickets && run_ends && tid == 0) ticket = __hip_atomic_fetch_add(p.tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -171,7 +181,14 @@ __global__ __launch_bounds__(64, 4) void spectrum64_kernel(const SpecParams p) {
     KSA_STAMP(10);
     finish_frame<N, T, S, CM>(p, red, frame, tid);
     KSA_STAMP(8);
+    ++frame;
+    if (run_ends) {
+      run = p.tickets ? ticket_next<T>(ticket, nullptr) : run + (int)gridDim.x;
+      frame = run * run_len;
+      f_hi = min(frame + run_len, p.nframes);
+    }
   }
+  KSA_SKEW_END();
 #ifdef KSA_STAMPS
   if (p.dbg && tid == 0)
     for (int i = 0; i < 12; ++i) p.dbg[(long long)blockIdx.x * 12 + i] = seg[i];

@@ -95,7 +95,15 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
   };
 
   const int npairs = (p.nframes + 1) / 2;
-  for (int pf = blockIdx.x; pf < npairs; pf += gridDim.x) {
+  // Pairs in runs of p.ticket_run consecutive ones, by ticket (spectrum_kernel / spectrum64_kernel hold the why); the hand-off
+  // word of a workgroup of several waves is the last one of the exchange buffer, behind the four output planes.
+  static_assert(4 * N * 4 + 4 <= NPAD * 16, "the ticket word sits behind the output planes");
+  unsigned* const next_word = reinterpret_cast<unsigned*>(lds2 + NPAD) - 1;
+  const int run_len = p.tickets ? p.ticket_run : 1;
+  int run = blockIdx.x, pf = run * run_len, pf_hi = min(pf + run_len, npairs);
+  KSA_SKEW_BEGIN();   // diagnostic builds only (ksa_kernels.hpp)
+  while (pf < npairs) {
+    KSA_SKEW_UNIT();
     const int fa = 2 * pf;
     const bool has_b = fa + 1 < p.nframes;
     const int fb = has_b ? fa + 1 : fa;          // an odd batch: the last workgroup transforms its frame twice
@@ -213,6 +221,9 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
     //      scratch plane finish_frame may use), then the common output stage, one frame after the other
     float* const red = reinterpret_cast<float*>(lds2);
     __syncthreads();
+    const bool run_ends = pf + 1 == pf_hi;
+    unsigned ticket = 0;
+    if (p.tickets && run_ends && l == 0) ticket = __hip_atomic_fetch_add(p.tickets, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       red[l + L * perm<16>(i)] = acc[i].x;
@@ -222,7 +233,14 @@ __global__ __launch_bounds__(Plan<N>::T, 2) void spectrum_pair_kernel(const Spec
     finish_frame<N, T, 1, CM>(p, red, fa, l);
     if (has_b) finish_frame<N, T, 1, CM>(p, red + 2 * N, fb, l);
     // (the next pair's first exchange barrier orders these LDS reads before its writes)
+    ++pf;
+    if (run_ends) {
+      run = p.tickets ? ticket_next<T>(ticket, next_word) : run + (int)gridDim.x;
+      pf = run * run_len;
+      pf_hi = min(pf + run_len, npairs);
+    }
   }
+  KSA_SKEW_END();
 }
 
 }  // namespace ksa
