@@ -30,6 +30,11 @@ extern "C" {
                              5: ksa_frames_c64 / ksa_frames_u8 (zeroSpan batches from host memory)
                              A binding takes the number from ksa_abi_version() of the library it loaded, never from a literal. */
 #define KSA_HM_ROWS 128 /* waterfall history depth: maxHM K:448, fftHMMax K:611 */
+/* Upper bounds that ksa_create enforces (a config past them is refused, nothing is allocated).  The kernels address a captured
+ * block in bytes with 32-bit offsets, so full_size * 8 (complex64, the widest sample) must stay below 2^31; the bound holds for
+ * every sample format since `fmt` arrives per call.  The scan kernels index the state float[4][scan_total_entries] with int. */
+#define KSA_MAX_FULL_SIZE 268435455          /* 2^28 - 1 samples */
+#define KSA_MAX_SCAN_TOTAL_ENTRIES 536870912 /* 2^29: 4 * total - 1 <= INT32_MAX */
 
 /* d['curScanCumuMode'] K:31-34, K:58, consumed by data_cumu K:124-147 */
 enum { KSA_CUMU_RAW = 0, KSA_CUMU_AVG = 1, KSA_CUMU_MAX = 2, KSA_CUMU_MIN = 3 };
@@ -109,9 +114,18 @@ typedef struct ksa_config {
   int32_t fft_size;             /* d['fftSize']: power of two, 16 .. 1048576; or 2^a*3^b*5^c, a multiple of 4, 16 .. 16384
                                    (the mixed-radix path; the layout and the calls are unchanged, so the ABI number is too:
                                    a library without that path refuses such sizes in ksa_create) */
-  int32_t full_size;            /* d['fullSize'] K:926-929: samples per captured block */
+  int32_t full_size;            /* d['fullSize'] K:926-929: samples per captured block, fft_size .. KSA_MAX_FULL_SIZE */
   int32_t num_windows;          /* windows actually transformed (K:385-390); KSA_CUMU_PFB / KSA_CUMU_PFB_PSD: the tap count P */
-  const int32_t* window_starts; /* host[num_windows]: iStart = int(i*fftSize*nonOverlap) K:386 */
+  const int32_t* window_starts; /* host[num_windows]: iStart = int(i*fftSize*nonOverlap) K:386.
+                                   The geometry is the caller's: every entry satisfies 0 <= start and start + fft_size <= full_size
+                                   (compared in 64 bits; anything else is refused by ksa_create), and nothing more is asked -- the
+                                   starts may come in any order, ascending, descending or shuffled, at any spacing, and a start may
+                                   be listed more than once (each listing is a window of its own).  The folds follow the LIST:
+                                   KSA_CUMU_RAW returns the window listed last; KSA_CUMU_AVG is the (a+x)/2 recursion of K:137-139
+                                   over the list, so the window at list position k weighs 2^-(num_windows-k) (position 0:
+                                   2^-(num_windows-1)) wherever it lies in the block; MAX, MIN and PSD do not depend on the order;
+                                   KSA_CUMU_PFB pairs window_starts[k] with tap segment k.  The `_dev` entry points accept every
+                                   frame_stride >= 0: 0 reads the same block nframes times and writes nframes equal rows. */
   const float* window;          /* host[fft_size]: d['theWin'] K:932-936; the length depends on the mode: KSA_CUMU_PFB and
                                    KSA_CUMU_PFB_PSD read host[num_windows*fft_size], the prototype filter */
   double mag_scale;             /* 2*winAdj/fftSize with winAdj = N/sum(win): K:373, K:391 */
@@ -120,9 +134,9 @@ typedef struct ksa_config {
   float min_amp;                /* d['minAmp4Clip'] K:53, K:101 */
   int32_t hm_width;             /* d['PltHeatMapWidth'] K:449-455 (zeroSpan) ; must divide fft_size (a power of two when fft_size is one) */
   int32_t max_frames;           /* largest batch handed to ksa_frames_dev / ksa_curscan_dev / steps per scan pass */
-  float u8_offset, u8_scale;    /* uint8 unpack (b - offset) / scale; 127.5 / 127.5 by default */
+  float u8_offset, u8_scale;    /* uint8 unpack (b - offset) / scale; 127.5 / 127.5 by default; u8_scale finite and non-zero */
   /* scan mode (0 = zeroSpan only): _scan_range K:568-698 */
-  int32_t scan_total_entries;   /* totalEntries = numGroups*fftSize K:599-600 */
+  int32_t scan_total_entries;   /* totalEntries = numGroups*fftSize K:599-600; 0 .. KSA_MAX_SCAN_TOTAL_ENTRIES */
   int32_t scan_hop;             /* fftSize*scanRangeNonOverlap (validated integral, K:591-593) */
   int32_t scan_hm_width;        /* d['xRes'] : width of the per-pass waterfall row K:614, K:697 */
 } ksa_config;

@@ -957,10 +957,15 @@ int validate_config(const ksa_config* cfg) {
   if (!mixed && (!is_pow2(n) || n < 16 || n > (1 << 20)))
     return fail("fft_size %d must be a power of two in 16..1048576, or 2^a*3^b*5^c, a multiple of 4, in 16..16384", n);
   if (cfg->full_size < n) return fail("full_size %d < fft_size %d", cfg->full_size, n);
+  // the spectrum kernels address a block in bytes with 32-bit offsets ((start + l) * SB, frame_len * SB): the bound is that of
+  // the widest sample (complex64, 8 bytes) so that it holds whatever `fmt` a later call names
+  if (cfg->full_size > KSA_MAX_FULL_SIZE)
+    return fail("full_size %d exceeds %d samples (32-bit byte offsets of 8-byte samples)", cfg->full_size, KSA_MAX_FULL_SIZE);
   if (cfg->num_windows < 1 || !cfg->window_starts || !cfg->window) return fail("window table / starts missing");
   for (int i = 0; i < cfg->num_windows; ++i)
-    if (cfg->window_starts[i] < 0 || cfg->window_starts[i] + n > cfg->full_size)
-      return fail("window %d start %d runs past the block", i, cfg->window_starts[i]);
+    if (cfg->window_starts[i] < 0 || (long long)cfg->window_starts[i] + n > (long long)cfg->full_size)
+      return fail("window_starts[%d] = %d: the window [%d, %lld) lies outside the block of full_size %d", i, cfg->window_starts[i],
+                  cfg->window_starts[i], (long long)cfg->window_starts[i] + n, cfg->full_size);
   if (cfg->cumu_mode < KSA_CUMU_RAW || cfg->cumu_mode > KSA_CUMU_PFB_PSD) return fail("unknown cumu_mode %d", cfg->cumu_mode);
   if (cfg->cumu_mode == KSA_CUMU_PFB && cfg->num_windows > KSA_PFB_MAX_TAPS)
     return fail("KSA_CUMU_PFB: num_windows %d outside 1..%d taps", cfg->num_windows, KSA_PFB_MAX_TAPS);
@@ -978,7 +983,10 @@ int validate_config(const ksa_config* cfg) {
   if (!mixed && (cfg->hm_width < 0 || (cfg->hm_width && (n % cfg->hm_width || !is_pow2(cfg->hm_width)))))
     return fail("hm_width %d must be a power of two dividing fft_size", cfg->hm_width);
   if (cfg->max_frames < 1) return fail("max_frames must be >= 1");
-  if (!(cfg->u8_scale != 0.f)) return fail("u8_scale must be non-zero");
+  if (!std::isfinite(cfg->u8_scale) || cfg->u8_scale == 0.f) return fail("u8_scale %g must be finite and non-zero", (double)cfg->u8_scale);
+  // the stitch, row and levels kernels index the state [4][scan_total_entries] in int: 3 * total + element < 2^31
+  if (cfg->scan_total_entries < 0 || cfg->scan_total_entries > KSA_MAX_SCAN_TOTAL_ENTRIES)
+    return fail("scan_total_entries %d outside 0..%d", cfg->scan_total_entries, KSA_MAX_SCAN_TOTAL_ENTRIES);
   if (cfg->scan_total_entries) {
     if (cfg->scan_hop < 1 || cfg->scan_hop > n) return fail("scan_hop %d outside 1..fft_size", cfg->scan_hop);
     if (cfg->scan_hm_width < 1 || cfg->scan_total_entries % cfg->scan_hm_width)

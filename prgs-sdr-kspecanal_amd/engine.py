@@ -152,7 +152,8 @@ class SpectrumEngine:
     def __init__(self, fft_size, full_size=None, sampling_rate=2.4e6, non_overlap=0.1, window="ones",
                  cumu_mode="AVG", gain=19.1, min_amp=MIN_AMP_DEFAULT, xres=512, max_frames=1, device=0,
                  scan_total_entries=0, scan_non_overlap=0.5, scan_xres=None,
-                 u8_offset=127.5, u8_scale=127.5, stream=None, psd_fs=2.0, pfb_taps=0, pfb_spectra=0):
+                 u8_offset=127.5, u8_scale=127.5, stream=None, psd_fs=2.0, pfb_taps=0, pfb_spectra=0,
+                 starts=None, mag_scale=None):
         """pfb_taps = P >= 1 turns the polyphase front end on (KSA_CUMU_PFB): every block is P segments of fftSize samples at
         k*fftSize, weighted by the prototype `window` -- a name (pfb_window(fftSize, P, name)) or an array of P*fftSize
         taps --, summed and transformed once; full_size defaults to P*fftSize, mag_scale = 2 / sum(taps) (K:373 / K:391 read
@@ -160,7 +161,11 @@ class SpectrumEngine:
         pfb_spectra = K >= 1 (needs pfb_taps) makes it the integrating polyphase spectrometer (KSA_CUMU_PFB_PSD): a block holds K
         sub-frames that advance by fftSize samples, each folded as above, and the engine returns the sum of their K power
         spectra; full_size defaults to (P+K-1)*fftSize and mag_scale = 1 / (psd_fs * sum(taps^2) * K), a density as under
-        cumu_mode PSD (unit-variance white noise reads 1/psd_fs)."""
+        cumu_mode PSD (unit-variance white noise reads 1/psd_fs).
+        starts / mag_scale: the caller's geometry instead of the derived one, in every mode (include/ksa.h: "the caller chooses
+        segmentation and scale").  starts = the window start offsets in list order (the polyphase modes: one per tap segment, so
+        pfb_taps of them) -- handed to the library as they are, which refuses what does not fit the block; under pfb_spectra the
+        count K then follows the header's formula from the largest start.  mag_scale replaces the derived scale."""
         self.fft_size = int(fft_size)
         if not fft_size_supported(self.fft_size):
             raise KsaError(fft_size_message(self.fft_size))
@@ -177,9 +182,15 @@ class SpectrumEngine:
         if self.pfb_taps and full_size is None:
             full_size = (self.pfb_taps + max(1, self.pfb_spectra) - 1) * self.fft_size
         self.full_size = int(full_size) if full_size is not None else full_size_for(self.fft_size, sampling_rate)
-        if self.pfb_taps and self.full_size < self.pfb_taps * self.fft_size:
+        custom = None if starts is None else np.ascontiguousarray(np.asarray(starts).reshape(-1), dtype=np.int32)
+        if custom is not None and self.pfb_taps and len(custom) != self.pfb_taps:
+            raise KsaError("starts has %d entries, pfb_taps is %d (one start per tap segment)" % (len(custom), self.pfb_taps))
+        pfb_psd = self.pfb_spectra > 0
+        if custom is not None and pfb_psd and len(custom):     # K of include/ksa.h, from the largest start wherever it is listed
+            self.pfb_spectra = (self.full_size - int(custom.max()) - self.fft_size) // self.fft_size + 1
+        if custom is None and self.pfb_taps and self.full_size < self.pfb_taps * self.fft_size:
             raise KsaError("fullSize %d holds fewer than pfb_taps %d segments of fftSize %d" % (self.full_size, self.pfb_taps, self.fft_size))
-        if self.pfb_spectra and self.full_size // self.fft_size - self.pfb_taps + 1 != self.pfb_spectra:
+        if custom is None and self.pfb_spectra and self.full_size // self.fft_size - self.pfb_taps + 1 != self.pfb_spectra:
             raise KsaError("fullSize %d holds %d spectra of pfb_taps %d x fftSize %d, pfb_spectra is %d" % (
                 self.full_size, self.full_size // self.fft_size - self.pfb_taps + 1, self.pfb_taps, self.fft_size, self.pfb_spectra))
         self.non_overlap = float(non_overlap)
@@ -200,18 +211,20 @@ class SpectrumEngine:
         self.win = win
         self.win_adj = self.fft_size / np.sum(win)                 # K:373 (the polyphase prototype: on the long window)
         if self.pfb_taps:
-            self.starts = np.arange(self.pfb_taps, dtype=np.int32) * np.int32(self.fft_size)
+            self.starts = np.arange(self.pfb_taps, dtype=np.int32) * np.int32(self.fft_size) if custom is None else custom
             self.mag_scale = 2.0 / float(np.sum(win))
-            if self.pfb_spectra:       # a power density, as under cumu_mode PSD
+            if pfb_psd:                # a power density, as under cumu_mode PSD
                 self.psd_fs = float(psd_fs)
-                self.mag_scale = psd_mag_scale(win, self.pfb_spectra, self.psd_fs)
+                self.mag_scale = psd_mag_scale(win, max(1, self.pfb_spectra), self.psd_fs)
         elif self.cumu_mode == "PSD":      # Welch PSD: matplotlib's segments and scale instead of K:386 / K:391
             self.psd_fs = float(psd_fs)
-            self.starts = psd_window_starts(self.full_size, self.fft_size, self.non_overlap)
-            self.mag_scale = psd_mag_scale(win, len(self.starts), self.psd_fs)
+            self.starts = psd_window_starts(self.full_size, self.fft_size, self.non_overlap) if custom is None else custom
+            self.mag_scale = psd_mag_scale(win, max(1, len(self.starts)), self.psd_fs)
         else:
-            self.starts = window_starts(self.full_size, self.fft_size, self.non_overlap)
+            self.starts = window_starts(self.full_size, self.fft_size, self.non_overlap) if custom is None else custom
             self.mag_scale = 2.0 * self.win_adj / self.fft_size    # K:391
+        if mag_scale is not None:
+            self.mag_scale = float(mag_scale)
         self.hm_width = heatmap_width(self.fft_size, int(xres))
         if self.fft_size % self.hm_width:
             raise KsaError("xRes %d does not divide fftSize %d (the reference fixes xRes up at K:937-949)" % (xres, fft_size))
@@ -232,7 +245,7 @@ class SpectrumEngine:
             window_starts=self._starts32.ctypes.data_as(C.POINTER(C.c_int32)),
             window=self._win32.ctypes.data_as(C.POINTER(C.c_float)),
             mag_scale=self.mag_scale,
-            cumu_mode=CUMU_PFB_PSD if self.pfb_spectra else CUMU_PFB if self.pfb_taps else CUMU[self.cumu_mode], gain=self.gain, min_amp=self.min_amp, hm_width=self.hm_width,
+            cumu_mode=CUMU_PFB_PSD if pfb_psd else CUMU_PFB if self.pfb_taps else CUMU[self.cumu_mode], gain=self.gain, min_amp=self.min_amp, hm_width=self.hm_width,
             max_frames=self.max_frames, u8_offset=u8_offset, u8_scale=u8_scale,
             scan_total_entries=self.scan_total, scan_hop=self.scan_hop, scan_hm_width=self.scan_hm_width)
         h = C.c_void_p()
