@@ -372,6 +372,12 @@ template <int N, int FMT, int RM, int CM>
 int launch_spec_c(ksa_engine* e, const SpecParams& p, bool configure_only) {
   using P = ksa::Plan<N>;
   auto kfn = ksa::spectrum_kernel<N, FMT, RM, CM>;
+#ifdef KSA_EXPERIMENTS
+  // KSA_PLAIN: the plain-arithmetic instantiation of a kernel that ships with packed butterflies (Tune<N>::packed)
+  if constexpr (ksa::Tune<N>::packed(RM)) {
+    if (exp_env("KSA_PLAIN")) kfn = ksa::spectrum_plain_kernel<N, FMT, RM, CM>;
+  }
+#endif
   static const int lds_pad = exp_env("KSA_LDS_PAD_KB") ? atoi(exp_env("KSA_LDS_PAD_KB")) * 1024 : 0;   // occupancy experiments
   const int lds_bytes = ksa::Tune<N>::LDS_BYTES + lds_pad;
   if (configure_only) {

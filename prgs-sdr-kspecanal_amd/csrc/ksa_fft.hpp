@@ -7,8 +7,14 @@
 // from HBM/L2 with the window multiply fused); passes 1..M-1 are radix 16 with one butterfly per
 // thread.  Between passes the 16 results are exchanged through LDS (Stockham autosort, so the
 // last pass leaves natural-order bins l + L*t in the registers of thread l).
+//
+// Arithmetic: every butterfly takes its complex primitives from a policy type, Scalar (plain fp32 VALU instructions, what
+// every kernel used up to round 5) or Packed (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 on the (re, im) register pair of ONE
+// complex value: one instruction where the plain form has two).  Both perform the same FMAs in the same order on the same
+// operands, so their results are the same bits; which kernels run the packed form is Tune<N>::packed (ksa_kernels.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace ksa {
 
@@ -18,6 +24,133 @@ __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(
 __device__ __forceinline__ float2 cmul(float2 a, float2 w) {
   return make_float2(fmaf(-a.y, w.y, a.x * w.x), fmaf(a.y, w.x, a.x * w.y));
 }
+
+
+// ---- the two arithmetic policies ------------------------------------------------------------------------------------
+// Scalar: the plain forms.  sub_j / add_j are a - j*b / a + j*b; fma is a + u*b as four FMAs and twice_minus the matching
+// a - u*b = 2a - (a + u*b); scale / fma_tap / fnma_tap take a real factor that is element H of the aligned pair wp (a window tap).
+struct Scalar {
+  static constexpr bool PACKED = false;
+  static __device__ __forceinline__ float2 add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+  static __device__ __forceinline__ float2 sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+  static __device__ __forceinline__ float2 sub_j(float2 a, float2 b) { return make_float2(a.x + b.y, a.y - b.x); }
+  static __device__ __forceinline__ float2 add_j(float2 a, float2 b) { return make_float2(a.x - b.y, a.y + b.x); }
+  static __device__ __forceinline__ float2 mul(float2 a, float2 w) {
+    return make_float2(fmaf(-a.y, w.y, a.x * w.x), fmaf(a.y, w.x, a.x * w.y));
+  }
+  static __device__ __forceinline__ float2 fma(float2 a, float2 u, float2 b) {
+    return make_float2(fmaf(-u.y, b.y, fmaf(u.x, b.x, a.x)), fmaf(u.y, b.x, fmaf(u.x, b.y, a.y)));
+  }
+  static __device__ __forceinline__ float2 twice_minus(float2 a, float2 s) {
+    return make_float2(fmaf(2.0f, a.x, -s.x), fmaf(2.0f, a.y, -s.y));
+  }
+  template <int H> static __device__ __forceinline__ float2 scale(float2 a, float2 wp) {
+    const float w = H ? wp.y : wp.x;
+    return make_float2(a.x * w, a.y * w);
+  }
+  template <int H> static __device__ __forceinline__ float2 fma_tap(float2 a, float2 wp, float2 t) {    // t + a*w
+    const float w = H ? wp.y : wp.x;
+    return make_float2(fmaf(a.x, w, t.x), fmaf(a.y, w, t.y));
+  }
+  template <int H> static __device__ __forceinline__ float2 fnma_tap(float2 a, float2 wp, float2 t) {   // t - a*w
+    const float w = H ? wp.y : wp.x;
+    return make_float2(fmaf(-a.x, w, t.x), fmaf(-a.y, w, t.y));
+  }
+};
+
+// Packed: the same operations as VOP3P instructions.  op_sel / op_sel_hi pick, per source, the half that the low / the high
+// result lane reads (0: .x, 1: .y; defaults 0 / 1), neg_lo / neg_hi negate a source for the low / the high lane.  So a source
+// with op_sel 0, op_sel_hi 0 is .x broadcast, with 1, 0 the swapped pair (.y, .x).  Written as inline assembly and not left
+// to hipcc's SLP vectorizer (the build keeps -fno-slp-vectorize: with it on, a radix-16 pass gets 78 pair-building moves).
+// The statements are not volatile: the scheduler moves them like any other arithmetic.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// A complex product and a complex multiply-add are two dependent instructions.  KSA_PK_FORM 1 (the default) writes each such pair
+// as ONE statement; 0 (A/B builds) as two.  hipcc's hazard recognizer puts an s_nop between two assembly statements of which the second
+// reads what the first wrote (it cannot see that a v_pk_*_f32 has no destination-select hazard): 146 of them per two windows in
+// form 0, 72 in form 1, which measured 1.3 % faster at config 2 (profiles/ab_packed.txt).
+#ifndef KSA_PK_FORM
+#define KSA_PK_FORM 1
+#endif
+#define KSA_PK2(OUT, INS, A, B, MODS) \
+  asm(INS " %0, %1, %2 " MODS : "=v"(OUT) : "v"(A), "v"(B))
+#define KSA_PK3(OUT, A, B, C, MODS) \
+  asm("v_pk_fma_f32 %0, %1, %2, %3 " MODS : "=v"(OUT) : "v"(A), "v"(B), "v"(C))
+struct Packed {
+  static constexpr bool PACKED = true;
+  static __device__ __forceinline__ f32x2 in(float2 a) { f32x2 r; r.x = a.x; r.y = a.y; return r; }
+  static __device__ __forceinline__ float2 out(f32x2 a) { return make_float2(a.x, a.y); }
+  static __device__ __forceinline__ float2 add(float2 a, float2 b) {
+    f32x2 d;
+    KSA_PK2(d, "v_pk_add_f32", in(a), in(b), "");
+    return out(d);
+  }
+  static __device__ __forceinline__ float2 sub(float2 a, float2 b) {
+    f32x2 d;
+    KSA_PK2(d, "v_pk_add_f32", in(a), in(b), "neg_lo:[0,1] neg_hi:[0,1]");
+    return out(d);
+  }
+  static __device__ __forceinline__ float2 sub_j(float2 a, float2 b) {     // (a.x + b.y, a.y - b.x)
+    f32x2 d;
+    KSA_PK2(d, "v_pk_add_f32", in(a), in(b), "op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,0] neg_hi:[0,1]");
+    return out(d);
+  }
+  static __device__ __forceinline__ float2 add_j(float2 a, float2 b) {     // (a.x - b.y, a.y + b.x)
+    f32x2 d;
+    KSA_PK2(d, "v_pk_add_f32", in(a), in(b), "op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,0]");
+    return out(d);
+  }
+#if KSA_PK_FORM == 1
+  static __device__ __forceinline__ float2 mul(float2 a, float2 w) {
+    f32x2 d;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]\n\t"
+        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[0,0,0]" : "=&v"(d) : "v"(in(a)), "v"(in(w)));
+    return out(d);
+  }
+  static __device__ __forceinline__ float2 fma(float2 a, float2 u, float2 b) {
+    f32x2 d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"
+        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[0,0,0]" : "=&v"(d) : "v"(in(u)), "v"(in(b)), "v"(in(a)));
+    return out(d);
+  }
+#else
+  static __device__ __forceinline__ float2 mul(float2 a, float2 w) {
+    f32x2 t, d;
+    KSA_PK2(t, "v_pk_mul_f32", in(a), in(w), "op_sel:[0,0] op_sel_hi:[0,1]");                        // a.x * (w.x, w.y)
+    KSA_PK3(d, in(a), in(w), t, "op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[0,0,0]");   // t + (-a.y * w.y, a.y * w.x)
+    return out(d);
+  }
+  static __device__ __forceinline__ float2 fma(float2 a, float2 u, float2 b) {
+    f32x2 t, d;
+    KSA_PK3(t, in(u), in(b), in(a), "op_sel:[0,0,0] op_sel_hi:[0,1,1]");                             // a + u.x * (b.x, b.y)
+    KSA_PK3(d, in(u), in(b), t, "op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[0,0,0]");   // t + (-u.y * b.y, u.y * b.x)
+    return out(d);
+  }
+#endif
+  static __device__ __forceinline__ float2 twice_minus(float2 a, float2 s) {
+    f32x2 d, two;
+    two.x = 2.0f; two.y = 2.0f;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(d) : "s"(two), "v"(in(a)), "v"(in(s)));   // the constant pair lives in SGPRs
+    return out(d);
+  }
+  template <int H> static __device__ __forceinline__ float2 scale(float2 a, float2 wp) {
+    f32x2 d;
+    if constexpr (H) KSA_PK2(d, "v_pk_mul_f32", in(a), in(wp), "op_sel:[0,1] op_sel_hi:[1,1]");
+    else KSA_PK2(d, "v_pk_mul_f32", in(a), in(wp), "op_sel:[0,0] op_sel_hi:[1,0]");
+    return out(d);
+  }
+  template <int H> static __device__ __forceinline__ float2 fma_tap(float2 a, float2 wp, float2 t) {
+    f32x2 d;
+    if constexpr (H) KSA_PK3(d, in(a), in(wp), in(t), "op_sel:[0,1,0] op_sel_hi:[1,1,1]");
+    else KSA_PK3(d, in(a), in(wp), in(t), "op_sel:[0,0,0] op_sel_hi:[1,0,1]");
+    return out(d);
+  }
+  template <int H> static __device__ __forceinline__ float2 fnma_tap(float2 a, float2 wp, float2 t) {
+    f32x2 d;
+    if constexpr (H) KSA_PK3(d, in(a), in(wp), in(t), "op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]");
+    else KSA_PK3(d, in(a), in(wp), in(t), "op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]");
+    return out(d);
+  }
+};
 
 constexpr float kSqrtHalf = 0.70710678118654752440f;
 constexpr float kCosPi8 = 0.92387953251128675613f;
@@ -52,16 +185,20 @@ __device__ __forceinline__ void dft2(float2 (&v)[SZ]) {
   v[BASE + STRIDE] = csub(a, b);
 }
 
-// natural-order in-place radix-4 on v[BASE + STRIDE*{0,1,2,3}]
-template <int BASE, int STRIDE, int SZ>
+// natural-order in-place radix-4 on v[BASE + STRIDE*{0,1,2,3}].  P02 / P13 = false keep the first-level sum and difference of
+// (a0, a2) / (a1, a3) in the plain form whatever A is: where one of the two is the product of mul_w16<2 | 6>, hipcc contracts
+// that multiply into the plain add (one FMA, one rounding), which a packed add of the rounded product would not reproduce.
+template <int BASE, int STRIDE, class A = Scalar, bool P02 = true, bool P13 = true, int SZ>
 __device__ __forceinline__ void dft4(float2 (&v)[SZ]) {
+  using A02 = std::conditional_t<P02, A, Scalar>;
+  using A13 = std::conditional_t<P13, A, Scalar>;
   float2 a0 = v[BASE], a1 = v[BASE + STRIDE], a2 = v[BASE + 2 * STRIDE], a3 = v[BASE + 3 * STRIDE];
-  float2 s0 = cadd(a0, a2), d0 = csub(a0, a2);
-  float2 s1 = cadd(a1, a3), d1 = csub(a1, a3);
-  v[BASE] = cadd(s0, s1);
-  v[BASE + 2 * STRIDE] = csub(s0, s1);
-  v[BASE + STRIDE] = make_float2(d0.x + d1.y, d0.y - d1.x);      // d0 - j*d1
-  v[BASE + 3 * STRIDE] = make_float2(d0.x - d1.y, d0.y + d1.x);  // d0 + j*d1
+  float2 s0 = A02::add(a0, a2), d0 = A02::sub(a0, a2);
+  float2 s1 = A13::add(a1, a3), d1 = A13::sub(a1, a3);
+  v[BASE] = A::add(s0, s1);
+  v[BASE + 2 * STRIDE] = A::sub(s0, s1);
+  v[BASE + STRIDE] = A::sub_j(d0, d1);      // d0 - j*d1
+  v[BASE + 3 * STRIDE] = A::add_j(d0, d1);  // d0 + j*d1
 }
 
 // radix-8 on v[BASE..BASE+7]; position BASE+P ends up holding X[perm8(P)]
@@ -142,34 +279,35 @@ __device__ __forceinline__ float2 twice_minus(float2 a, float2 s) {
   return make_float2(fmaf(2.0f, a.x, -s.x), fmaf(2.0f, a.y, -s.y));
 }
 
-// radix-4 of (a0, u1*a1, u2*a2, u3*a3) in 24 VALU ops (plain: 12 for the products + 16)
-template <int BASE, int STRIDE, int SZ>
+// radix-4 of (a0, u1*a1, u2*a2, u3*a3) in 24 VALU ops (plain: 12 for the products + 16); 12 packed ones
+template <int BASE, int STRIDE, class A = Scalar, int SZ>
 __device__ __forceinline__ void dft4_tw(float2 (&v)[SZ], float2 u1, float2 u2, float2 u3) {
   const float2 a0 = v[BASE], a1 = v[BASE + STRIDE], a2 = v[BASE + 2 * STRIDE], a3 = v[BASE + 3 * STRIDE];
-  const float2 s02 = cfma(a0, u2, a2);
-  const float2 d02 = twice_minus(a0, s02);
-  const float2 t1 = cmul(a1, u1);
-  const float2 s13 = cfma(t1, u3, a3);
-  const float2 d13 = twice_minus(t1, s13);
-  v[BASE] = cadd(s02, s13);
-  v[BASE + 2 * STRIDE] = csub(s02, s13);
-  v[BASE + STRIDE] = make_float2(d02.x + d13.y, d02.y - d13.x);      // d02 - j*d13
-  v[BASE + 3 * STRIDE] = make_float2(d02.x - d13.y, d02.y + d13.x);  // d02 + j*d13
+  const float2 s02 = A::fma(a0, u2, a2);
+  const float2 d02 = A::twice_minus(a0, s02);
+  const float2 t1 = A::mul(a1, u1);
+  const float2 s13 = A::fma(t1, u3, a3);
+  const float2 d13 = A::twice_minus(t1, s13);
+  v[BASE] = A::add(s02, s13);
+  v[BASE + 2 * STRIDE] = A::sub(s02, s13);
+  v[BASE + STRIDE] = A::sub_j(d02, d13);      // d02 - j*d13
+  v[BASE + 3 * STRIDE] = A::add_j(d02, d13);  // d02 + j*d13
 }
 
 // radix-16 of (w^t * v[t]), t = 4*n1 + n2, with all twiddles folded into the two radix-4 levels:
 // level A uses w^4, w^8, w^12; level B uses c[n2][k1] = w^n2 * W16^(n2*k1).  tw[] holds them in the
 // order {w4, w8, w12, c10, c20, c30, c11, c21, c31, c12, c22, c32, c13, c23, c33} (c<n2><k1>).
 // 192 VALU ops instead of 256 for "multiply then transform".  Position P ends up holding X[perm16(P)].
+template <class A = Scalar>
 __device__ __forceinline__ void dft16_fused(float2 (&v)[16], const float2 (&tw)[15]) {
-  dft4_tw<0, 4>(v, tw[0], tw[1], tw[2]);
-  dft4_tw<1, 4>(v, tw[0], tw[1], tw[2]);
-  dft4_tw<2, 4>(v, tw[0], tw[1], tw[2]);
-  dft4_tw<3, 4>(v, tw[0], tw[1], tw[2]);
-  dft4_tw<0, 1>(v, tw[3], tw[4], tw[5]);
-  dft4_tw<4, 1>(v, tw[6], tw[7], tw[8]);
-  dft4_tw<8, 1>(v, tw[9], tw[10], tw[11]);
-  dft4_tw<12, 1>(v, tw[12], tw[13], tw[14]);
+  dft4_tw<0, 4, A>(v, tw[0], tw[1], tw[2]);
+  dft4_tw<1, 4, A>(v, tw[0], tw[1], tw[2]);
+  dft4_tw<2, 4, A>(v, tw[0], tw[1], tw[2]);
+  dft4_tw<3, 4, A>(v, tw[0], tw[1], tw[2]);
+  dft4_tw<0, 1, A>(v, tw[3], tw[4], tw[5]);
+  dft4_tw<4, 1, A>(v, tw[6], tw[7], tw[8]);
+  dft4_tw<8, 1, A>(v, tw[9], tw[10], tw[11]);
+  dft4_tw<12, 1, A>(v, tw[12], tw[13], tw[14]);
 }
 
 // ---- 32 points per thread (ksa_kernels32.hpp) -----------------------------------------------------------
@@ -280,6 +418,8 @@ __host__ __device__ constexpr int perm32(int p) { return 2 * (((p & 15) >> 2) | 
 // Second radix-4 level of an untwiddled radix-16: group k1 takes its inputs times W16^(n2*k1).  (The FMA-fused form
 // with the constants as twiddles -- 24 instead of 28 instructions for groups 1 and 3 -- measured 1 % SLOWER at config 2:
 // longer dependent chains, constants through SGPRs)
+// Packed: the constant rotations stay plain, and with them the first-level sums that take a mul_w16<2 | 6> product (dft4).
+template <class A = Scalar>
 __device__ __forceinline__ void dft16_level_b(float2 (&v)[16]) {
   v[5] = mul_w16<1>(v[5]);
   v[6] = mul_w16<2>(v[6]);
@@ -290,10 +430,10 @@ __device__ __forceinline__ void dft16_level_b(float2 (&v)[16]) {
   v[13] = mul_w16<3>(v[13]);
   v[14] = mul_w16<6>(v[14]);
   v[15] = mul_w16<9>(v[15]);
-  dft4<0, 1>(v);
-  dft4<4, 1>(v);
-  dft4<8, 1>(v);
-  dft4<12, 1>(v);
+  dft4<0, 1, A>(v);
+  dft4<4, 1, A, false, true>(v);
+  dft4<8, 1, A, true, false>(v);
+  dft4<12, 1, A, false, true>(v);
 }
 
 // ---- first pass with the window multiply folded in ---------------------------------------------------------
@@ -301,36 +441,40 @@ __device__ __forceinline__ void dft16_level_b(float2 (&v)[16]) {
 // one product and two FMAs per component.  hipcc's FMA fusion reaches the same instruction count from the separate
 // multiply (PMC: unchanged), but the explicit form schedules better: +1.6 % at config 2.
 // v holds the RAW samples, w the matching taps.
-template <int BASE, int STRIDE, int SZ>
+// v holds the RAW samples, w the matching taps.  A tap enters as one half of the aligned pair (w[2i], w[2i + 1]) it sits in:
+// the packed form broadcasts it with op_sel and needs no copy.
+template <int BASE, int STRIDE, class A = Scalar, int SZ>
 __device__ __forceinline__ void dft4_win(float2 (&v)[SZ], const float (&w)[SZ]) {
   const float2 a0 = v[BASE], a1 = v[BASE + STRIDE], a2 = v[BASE + 2 * STRIDE], a3 = v[BASE + 3 * STRIDE];
-  const float w0 = w[BASE], w1 = w[BASE + STRIDE], w2 = w[BASE + 2 * STRIDE], w3 = w[BASE + 3 * STRIDE];
-  const float2 t0 = make_float2(a0.x * w0, a0.y * w0), t1 = make_float2(a1.x * w1, a1.y * w1);
-  const float2 s0 = make_float2(fmaf(a2.x, w2, t0.x), fmaf(a2.y, w2, t0.y));
-  const float2 d0 = make_float2(fmaf(-a2.x, w2, t0.x), fmaf(-a2.y, w2, t0.y));
-  const float2 s1 = make_float2(fmaf(a3.x, w3, t1.x), fmaf(a3.y, w3, t1.y));
-  const float2 d1 = make_float2(fmaf(-a3.x, w3, t1.x), fmaf(-a3.y, w3, t1.y));
-  v[BASE] = cadd(s0, s1);
-  v[BASE + 2 * STRIDE] = csub(s0, s1);
-  v[BASE + STRIDE] = make_float2(d0.x + d1.y, d0.y - d1.x);      // d0 - j*d1
-  v[BASE + 3 * STRIDE] = make_float2(d0.x - d1.y, d0.y + d1.x);  // d0 + j*d1
+  constexpr int I0 = BASE, I1 = BASE + STRIDE, I2 = BASE + 2 * STRIDE, I3 = BASE + 3 * STRIDE;
+  const float2 w0 = make_float2(w[I0 & ~1], w[I0 | 1]), w1 = make_float2(w[I1 & ~1], w[I1 | 1]);
+  const float2 w2 = make_float2(w[I2 & ~1], w[I2 | 1]), w3 = make_float2(w[I3 & ~1], w[I3 | 1]);
+  const float2 t0 = A::template scale<I0 & 1>(a0, w0), t1 = A::template scale<I1 & 1>(a1, w1);
+  const float2 s0 = A::template fma_tap<I2 & 1>(a2, w2, t0);
+  const float2 d0 = A::template fnma_tap<I2 & 1>(a2, w2, t0);
+  const float2 s1 = A::template fma_tap<I3 & 1>(a3, w3, t1);
+  const float2 d1 = A::template fnma_tap<I3 & 1>(a3, w3, t1);
+  v[BASE] = A::add(s0, s1);
+  v[BASE + 2 * STRIDE] = A::sub(s0, s1);
+  v[BASE + STRIDE] = A::sub_j(d0, d1);      // d0 - j*d1
+  v[BASE + 3 * STRIDE] = A::add_j(d0, d1);  // d0 + j*d1
 }
 
 // dft_first<R0> on raw samples and their taps (R0 = 16 or 4); same output positions as dft_first
-template <int R0>
+template <int R0, class A = Scalar>
 __device__ __forceinline__ void dft_first_win(float2 (&v)[16], const float (&w)[16]) {
   static_assert(R0 == 16 || R0 == 4, "windowed first pass: radix 16 or 4");
   if constexpr (R0 == 16) {
-    dft4_win<0, 4>(v, w);
-    dft4_win<1, 4>(v, w);
-    dft4_win<2, 4>(v, w);
-    dft4_win<3, 4>(v, w);
-    dft16_level_b(v);
+    dft4_win<0, 4, A>(v, w);
+    dft4_win<1, 4, A>(v, w);
+    dft4_win<2, 4, A>(v, w);
+    dft4_win<3, 4, A>(v, w);
+    dft16_level_b<A>(v);
   } else {
-    dft4_win<0, 1>(v, w);
-    dft4_win<4, 1>(v, w);
-    dft4_win<8, 1>(v, w);
-    dft4_win<12, 1>(v, w);
+    dft4_win<0, 1, A>(v, w);
+    dft4_win<4, 1, A>(v, w);
+    dft4_win<8, 1, A>(v, w);
+    dft4_win<12, 1, A>(v, w);
   }
 }
 

@@ -1,6 +1,6 @@
 // One window of spectrum_kernel's loop (ksa_kernels.hpp includes this text inside the kernel: once in the rolled loop, twice --
-// with PAR = 0 and PAR = 1 -- in the ping-pong form of the 50 %-overlap kernels of N = 4096).  Expects in scope: rd, PAR and
-// everything the kernel has set up in front of its window loop.  Sample q of the window sits in raw[(q + 8*PAR) & 15].
+// with PAR = 0 and PAR = 1 -- in the ping-pong form of the 50 %-overlap kernels of N = 4096).  Expects in scope: rd, PAR, the
+// arithmetic policy AR (ksa_fft.hpp) and everything the kernel has set up in front of its window loop.  Sample q of the window sits in raw[(q + 8*PAR) & 15].
       const int k = k_lo + (S == 1 ? rd : rd * S + slot);   // wave-uniform when one transform fills the workgroup
       const bool active = S == 1 || k < k_hi;
       float2 v[16];
@@ -56,7 +56,7 @@
       }
       KSA_STAMP(0);
       if (active) {
-        if constexpr (Tune<N>::WIN_FUSED) dft_first_win<R0>(v, wpos);
+        if constexpr (Tune<N>::WIN_FUSED) dft_first_win<R0, AR>(v, wpos);
         else dft_first<R0>(v);
       }
       KSA_STAMP(1);
@@ -73,7 +73,7 @@
           quad_transpose4(v[4 * b].y, v[4 * b + 1].y, v[4 * b + 2].y, v[4 * b + 3].y, odd1, odd2);
         }
         if (active) {
-          if constexpr (FUSED_LAST) dft16_fused(v, reinterpret_cast<const float2(&)[15]>(twl));
+          if constexpr (FUSED_LAST) dft16_fused<AR>(v, reinterpret_cast<const float2(&)[15]>(twl));
           else dft16_tw(v, twl[0], twl[1], twl[2], twl[3], twl[4], twl[5]);
         }
       } else if constexpr (M >= 2) {
@@ -114,17 +114,17 @@
             if (s < M - 1) {
               const float2* tw = tw_lds + tw_off + (l & (pp - 1));
               if constexpr (TWM_REGS) {
-                dft16_fused(v, reinterpret_cast<const float2(&)[15]>(twm));
+                dft16_fused<AR>(v, reinterpret_cast<const float2(&)[15]>(twm));
               } else if constexpr (FUSED) {
                 float2 tm[15];
 #pragma unroll
                 for (int e = 0; e < 15; ++e) tm[e] = tw[e * pp];
-                dft16_fused(v, tm);
+                dft16_fused<AR>(v, tm);
               } else {
                 dft16_tw(v, tw[0], tw[pp], tw[2 * pp], tw[3 * pp], tw[7 * pp], tw[11 * pp]);
               }
             } else {
-              if constexpr (FUSED_LAST) dft16_fused(v, reinterpret_cast<const float2(&)[15]>(twl));
+              if constexpr (FUSED_LAST) dft16_fused<AR>(v, reinterpret_cast<const float2(&)[15]>(twl));
               else dft16_tw(v, twl[0], twl[1], twl[2], twl[3], twl[4], twl[5]);
             }
           }
