@@ -1,7 +1,8 @@
 """Build libksa.so (HIP kernels + C ABI) for gfx950 with hipcc.  In-tree, no JIT cache:
 the .so sits next to this file so that it travels to the GPU box with the repo snapshot.
 Beside it libksa_exp.so, the same sources with -DKSA_EXPERIMENTS: the only build that reads the KSA_* environment
-switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel through it); the package never loads it."""
+switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel through it); the package never loads it.
+And libksa_density.so, the companion library of include/ksa_density.h, from its own sources under csrc_density/."""
 import os
 import shutil
 import subprocess
@@ -11,6 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "ksa_api.hip")
 OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
+SRC_DENSITY = os.path.join(HERE, "csrc_density", "ksd_api.hip")
+OUT_DENSITY = os.path.join(HERE, "libksa_density.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
@@ -20,21 +23,27 @@ def sources():
     return [os.path.join(d, f) for f in sorted(os.listdir(d))] + [os.path.join(HERE, "..", "include", "ksa.h")]
 
 
+def density_sources():
+    d = os.path.join(HERE, "csrc_density")
+    return [os.path.join(d, f) for f in sorted(os.listdir(d))] + [os.path.join(HERE, "..", "include", "ksa_density.h")]
+
+
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(s) > t for s in sources())
+    srcs = density_sources() if out == OUT_DENSITY else sources()
+    return any(os.path.getmtime(s) > t for s in srcs)
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the two libraries side by side).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the three libraries side by side).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, extra in ((OUT, []), (OUT_EXP, ["-DKSA_EXPERIMENTS"])):
+    for out, src, extra in ((OUT, SRC, []), (OUT_EXP, SRC, ["-DKSA_EXPERIMENTS"]), (OUT_DENSITY, SRC_DENSITY, [])):
         if not force and not is_stale(out):
             continue
-        cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", SRC]
+        cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]
         if verbose:
             print(" ".join(cmd))
         jobs.append((out, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

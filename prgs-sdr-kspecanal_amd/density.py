@@ -1,0 +1,197 @@
+"""Spectrum density (persistence) histogram on the GPU: ctypes binding of include/ksa_density.h (libksa_density.so, the
+companion of libksa.so) and the SpectrumDensity class over it.  A bitmap of level against frequency, each cell counting how
+many spectra passed through that level at that frequency; it consumes the per-frame dB rows the engine already writes to
+device memory (frames_dev(cur_db=...), curscan_dev(out_mode=OUT_DB)).  There is no fallback: a missing library raises."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from ._lib import KsaError
+from .engine import _ptr
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libksa_density.so")
+ABI_VERSION = 1
+
+_P = C.c_void_p
+_I32, _I64 = C.c_int32, C.c_int64
+
+# name -> (restype, argtypes); every symbol include/ksa_density.h declares
+SIGNATURES = {
+    "ksd_abi_version": (C.c_int, []),
+    "ksd_last_error": (C.c_char_p, []),
+    "ksd_create": (C.c_int, [_I32, _I32, _I32, _I32, C.c_float, C.c_float, C.POINTER(_P)]),
+    "ksd_destroy": (None, [_P]),
+    "ksd_set_stream": (C.c_int, [_P, _P]),
+    "ksd_synchronize": (C.c_int, [_P]),
+    "ksd_add_rows_dev": (C.c_int, [_P, _P, _I64, _I64]),
+    "ksd_add_rows": (C.c_int, [_P, _P, _I64]),
+    "ksd_decay": (C.c_int, [_P, _I64, _I64]),
+    "ksd_merge_dev": (C.c_int, [_P, _P, _I64]),
+    "ksd_reset": (C.c_int, [_P]),
+    "ksd_read": (C.c_int, [_P, _P, C.POINTER(_I64)]),
+    "ksd_counts_dev": (C.c_int, [_P, C.POINTER(_P)]),
+    "ksd_kernel_info": (C.c_int, [_P] + [C.POINTER(_I32)] * 6),
+}
+
+
+def load(path=LIB_PATH):
+    _lib._preload_torch_hip_runtime()      # both libraries bind the one HIP runtime torch mapped
+    if not os.path.exists(path):
+        raise KsaError("libksa_density.so is missing at %s -- build it with `python __graft_entry__.py` "
+                       "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
+    lib = C.CDLL(path)
+    lib.ksd_abi_version.restype = C.c_int
+    if lib.ksd_abi_version() != ABI_VERSION:
+        raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
+                       % (path, lib.ksd_abi_version(), ABI_VERSION))
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
+_loaded = None
+
+
+def lib():
+    """libksa_density.so, loaded on first use (the spectrum engine alone does not need it)."""
+    global _loaded
+    if _loaded is None:
+        _loaded = load()
+    return _loaded
+
+
+def check(rc):
+    if rc != 0:
+        raise KsaError(lib().ksd_last_error().decode("utf-8", "replace"))
+
+
+class _CountsView:
+    """View of the library-owned counters for torch.as_tensor (via __cuda_array_interface__)."""
+
+    def __init__(self, ptr, shape, owner):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i8", "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+class SpectrumDensity:
+    """int64 counts[levels + 1][width] on one GPU: row k < levels counts the dB values in [lo + k*step, lo + (k+1)*step) (the
+    first and last level also take what lies below and above the range), the extra last row counts NaNs; width must divide
+    nbins and nbins / width adjacent bins share a column.  The float32 rule is stated in include/ksa_density.h."""
+
+    def __init__(self, nbins, width=None, levels=256, lo_db=-140.0, hi_db=0.0, device=0, stream=None):
+        self.nbins = int(nbins)
+        self.width = self.nbins if width is None else int(width)
+        self.levels = int(levels)
+        self.lo_db, self.hi_db = float(lo_db), float(hi_db)
+        self.device = int(device)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().ksd_create(self.device, self.nbins, self.width, self.levels, self.lo_db, self.hi_db, C.byref(h)))
+        self._h = h
+        if stream is not None:
+            self.set_stream(stream)
+
+    # -- lifetime ---------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ksd_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream):
+        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
+        check(lib().ksd_set_stream(self._h, C.c_void_p(stream or 0)))
+
+    def synchronize(self):
+        check(lib().ksd_synchronize(self._h))
+
+    def kernel_info(self):
+        v = [C.c_int32() for _ in range(6)]
+        check(lib().ksd_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("threads", "lds_bytes", "vgprs", "grid", "strip_cols", "lds_optin"), [x.value for x in v]))
+
+    # -- counting ---------------------------------------------------------------------------------
+    def add_rows_dev(self, rows, nrows, row_stride=None):
+        """nrows float32 rows from device memory (a torch tensor, DevArray pointer or int address), row i at
+        rows + i*row_stride floats; asynchronous on the object's stream."""
+        stride = self.nbins if row_stride is None else int(row_stride)
+        check(lib().ksd_add_rows_dev(self._h, _ptr(rows), stride, int(nrows)))
+
+    def add_rows(self, host_rows):
+        """float32 [k][nbins] (or one row) from host memory; synchronises."""
+        a = np.ascontiguousarray(host_rows, dtype=np.float32)
+        if a.size % self.nbins or (a.ndim > 1 and a.shape[-1] != self.nbins):
+            raise KsaError("add_rows wants [k][%d] float32, got %s" % (self.nbins, a.shape))
+        if a.size:
+            check(lib().ksd_add_rows(self._h, _ptr(a), a.size // self.nbins))
+
+    def decay(self, num, den):
+        """Every count becomes floor(count * num / den), 0 <= num <= den < 2^31; rows_seen stays."""
+        if not (-2 ** 63 <= int(num) < 2 ** 63 and -2 ** 63 <= int(den) < 2 ** 63):
+            raise KsaError("decay(%d, %d): outside int64" % (num, den))
+        check(lib().ksd_decay(self._h, int(num), int(den)))
+
+    def merge_dev(self, counts, rows_seen_add=0):
+        """counts += another histogram of the same shape in device memory (int64 [levels + 1][width])."""
+        check(lib().ksd_merge_dev(self._h, _ptr(counts), int(rows_seen_add)))
+
+    def reset(self):
+        check(lib().ksd_reset(self._h))
+
+    def read(self):
+        """(counts int64 [levels + 1, width], rows_seen); synchronises."""
+        out = np.empty((self.levels + 1, self.width), dtype=np.int64)
+        seen = C.c_int64()
+        check(lib().ksd_read(self._h, _ptr(out), C.byref(seen)))
+        return out, seen.value
+
+    @property
+    def rows_seen(self):
+        seen = C.c_int64()
+        check(lib().ksd_read(self._h, None, C.byref(seen)))
+        return seen.value
+
+    def counts_dev(self):
+        p = C.c_void_p()
+        check(lib().ksd_counts_dev(self._h, C.byref(p)))
+        return _CountsView(p.value, (self.levels + 1, self.width), self)
+
+    # -- host helpers -----------------------------------------------------------------------------
+    def level_edges(self):
+        """float64 [levels + 1]: lo + k*(hi - lo)/levels, the nominal edges of the levels (the float32 rule decides hits)."""
+        return level_edges(self.levels, self.lo_db, self.hi_db)
+
+    @staticmethod
+    def image(counts, normalize="column", log=False):
+        return image(counts, normalize, log)
+
+
+def level_edges(levels, lo_db, hi_db):
+    return lo_db + np.arange(levels + 1, dtype=np.float64) * (hi_db - lo_db) / levels
+
+
+def image(counts, normalize="column", log=False):
+    """float32 [levels, width] in 0..1 from counts [levels + 1, width] (the NaN row dropped, level 0 first): ready for
+    imshow(origin="lower").  normalize "column": each column by its own largest cell (a weak burst beside a strong carrier
+    stays visible); "max": by the largest cell of the bitmap.  log: log1p of the counts first."""
+    c = np.asarray(counts)[:-1].astype(np.float64)
+    if log:
+        c = np.log1p(c)
+    if normalize == "column":
+        top = c.max(axis=0, keepdims=True)
+    elif normalize == "max":
+        top = np.full((1, c.shape[1]), c.max() if c.size else 0.0)
+    else:
+        raise KsaError("image: normalize [%s] is neither column nor max" % normalize)
+    return (c / np.where(top > 0, top, 1.0)).astype(np.float32)

@@ -13,7 +13,10 @@ arrays handed to matplotlib: d['Fft.Cur'|'Fft.Max'|'Fft.Min'|'Fft.Avg'], the fre
 `device`, `iqFormat` (c64|u8|s8|s16), `frameBatch` (zeroSpan blocks per device call, default 1), `pfbTaps` (P >= 1: the
 polyphase filter bank front end -- P*fftSize samples per spectrum, weighted by a sinc prototype tapered with `window`, folded
 onto fftSize points and transformed once; default 0 = off), `pfbSpectra` (K >= 1, with pfbTaps: the integrating polyphase
-spectrometer -- a block of (P+K-1)*fftSize samples holds K such spectra, summed as power, a density; default 0 = off).
+spectrometer -- a block of (P+K-1)*fftSize samples holds K such spectra, summed as power, a density; default 0 = off),
+`density` (L:lo:hi, zeroSpan only: a density / persistence histogram of every frame's dB spectrum, L levels over [lo, hi) dB
+against the waterfall's columns, handed off as d['density'], d['densityNaN'], d['densityEdges'], d['densityRows'];
+default empty = off) and `densitySave` (a file that takes the [L+1, W] int64 counts, NaN row last, with np.save).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -35,6 +38,7 @@ import numpy as np
 from . import engine as _engine
 from .engine import SpectrumEngine, KsaError, FMT_C64, FMT_U8
 from . import sources
+from .density import SpectrumDensity
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -64,6 +68,7 @@ _KEYS = {
     # additive keys of this build
     "SOURCE": ("source", str), "DEVICE": ("device", int), "IQFORMAT": ("iqFormat", str.lower),
     "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int), "PFBSPECTRA": ("pfbSpectra", int),
+    "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str),
 }
 
 
@@ -79,6 +84,7 @@ def defaults():
         "bGrid": True, "bUsePSD": False, "bScanRangeBaseDataIsRaw": False,
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
+        "density": "", "densitySave": "",
     }
 
 
@@ -159,7 +165,36 @@ def handle_args(d, argv=None):
     if d["bUsePSD"] and d["frameBatch"] > 1:
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] needs bUsePSD false: the PSD diagnostic is per block".format(d["frameBatch"]))
     _handle_pfb(d)
+    _handle_density(d)
     return d
+
+
+DENSITY_RULE = "density wants L:lo:hi with an integer 1 <= L <= 1024 levels and finite lo < hi in dB"
+
+
+def _handle_density(d):
+    """density L:lo:hi (additive, zeroSpan only): d['density.spec'] = (L, lo, hi), or None when the key is off."""
+    d["density.spec"] = None
+    text = d["density"]
+    if not text:
+        if d["densitySave"]:
+            print("WARN:handle_args: densitySave [{}] is ignored without density".format(d["densitySave"]))
+        return
+    try:
+        levels, lo, hi = text.split(":")
+        levels, lo, hi = int(levels), float(lo), float(hi)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: density [{}]: {}".format(text, DENSITY_RULE))
+    if not (1 <= levels <= 1024 and np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        prg_quit(d, "ERROR:handle_args: density [{}]: {}".format(text, DENSITY_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: density [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: density [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: density [{}] needs bUsePSD false: it counts the engine's own dB rows".format(text))
+    d["density.spec"] = (levels, lo, hi)
 
 
 def _handle_pfb(d):
@@ -654,13 +689,38 @@ def zero_span(d):
     eng = get_engine(d, max_frames=batch)
     eng.reset()
     d["fftHM"], d["fftHMIndex"] = np.zeros((_engine.HM_ROWS, eng.hm_width)), 0     # K:456; the device ring starts the same
-    if batch > 1:
-        _zero_span_batches(d, eng, freqs, batch)
-    else:
-        _zero_span_frames(d, eng, freqs)
+    spec = d.get("density.spec") if sdr_curscan is _gpu_curscan else None
+    dens = None
+    if spec is not None:                         # its columns are the waterfall's
+        dens = SpectrumDensity(d["fftSize"], eng.hm_width, spec[0], spec[1], spec[2], device=d["device"])
+    try:
+        if batch > 1 or dens is not None:        # the density is fed by the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens)
+        else:
+            _zero_span_frames(d, eng, freqs)
+        if dens is not None:
+            _density_handoff(d, dens)
+    finally:
+        if dens is not None:
+            dens.close()
     if _materialize(d, eng)["frames"] == 0:      # full-width arrays once, for SaveSigLvls and whoever called main()
         for k in ("Fft.Max", "Fft.Min", "Fft.Avg", "Fft.Cur"):
             d[k] = None                          # no frame ran: the curves are still None (K:427-430)
+
+
+def _density_handoff(d, dens):
+    """The density's hand-off arrays (drawing the bitmap is the caller's: density.image), the INFO line, densitySave."""
+    counts, rows = dens.read()
+    levels = dens.levels
+    d["density"], d["densityNaN"] = counts[:levels], counts[levels]
+    d["densityEdges"], d["densityRows"] = dens.level_edges(), rows
+    total = int(counts.sum())
+    clamped = int(counts[0].sum()) + (int(counts[levels - 1].sum()) if levels > 1 else 0)
+    print("INFO:zero_span: density rows [{}], levels [{}] x columns [{}], share of counts in the two clamped levels [{:.6f}]".format(
+        rows, levels, dens.width, clamped / total if total else 0.0))
+    if d["densitySave"]:
+        with open(d["densitySave"], "wb") as f:
+            np.save(f, counts)                   # [L+1, W] int64, the NaN row last
 
 
 def _zero_span_frames(d, eng, freqs):
@@ -689,12 +749,12 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch):
+def _zero_span_batches(d, eng, freqs, batch, dens=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
     frames, and a source that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of
-    frameBatch 1."""
+    frameBatch 1.  With a density object every batch also returns its frames' dB rows, which the object counts."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
     full = d["fullSize"]
     dtype, per = raw_dtype(u8)
@@ -719,8 +779,10 @@ def _zero_span_batches(d, eng, freqs, batch):
                         got += 1
                 except EOFError:
                     pass
-            if got:
+            if got and dens is None:
                 eng.frames(blocks[:got])                                     # K:464-484 for the whole batch, one call
+            elif got:
+                dens.add_rows(eng.frames(blocks[:got], cur_db=True)[0])
             done += got
             if got < k:
                 prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)
