@@ -2,7 +2,8 @@
 the .so sits next to this file so that it travels to the GPU box with the repo snapshot.
 Beside it libksa_exp.so, the same sources with -DKSA_EXPERIMENTS: the only build that reads the KSA_* environment
 switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel through it); the package never loads it.
-And libksa_density.so, the companion library of include/ksa_density.h, from its own sources under csrc_density/."""
+And libksa_density.so and libksa_mask.so, the companion libraries of include/ksa_density.h and include/ksa_mask.h, each from
+its own sources under csrc_density/ and csrc_mask/."""
 import os
 import shutil
 import subprocess
@@ -14,33 +15,50 @@ OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 SRC_DENSITY = os.path.join(HERE, "csrc_density", "ksd_api.hip")
 OUT_DENSITY = os.path.join(HERE, "libksa_density.so")
+SRC_MASK = os.path.join(HERE, "csrc_mask", "ksm_api.hip")
+OUT_MASK = os.path.join(HERE, "libksa_mask.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
 
+def _tree(subdir, header):
+    d = os.path.join(HERE, subdir)
+    return [os.path.join(d, f) for f in sorted(os.listdir(d))] + [os.path.join(HERE, "..", "include", header)]
+
+
 def sources():
-    d = os.path.join(HERE, "csrc")
-    return [os.path.join(d, f) for f in sorted(os.listdir(d))] + [os.path.join(HERE, "..", "include", "ksa.h")]
+    return _tree("csrc", "ksa.h")
 
 
 def density_sources():
-    d = os.path.join(HERE, "csrc_density")
-    return [os.path.join(d, f) for f in sorted(os.listdir(d))] + [os.path.join(HERE, "..", "include", "ksa_density.h")]
+    return _tree("csrc_density", "ksa_density.h")
+
+
+def mask_sources():
+    return _tree("csrc_mask", "ksa_mask.h")
+
+
+# product -> (the .hip that is compiled, extra flags, every file the product depends on)
+JOBS = {
+    OUT: (SRC, [], sources),
+    OUT_EXP: (SRC, ["-DKSA_EXPERIMENTS"], sources),
+    OUT_DENSITY: (SRC_DENSITY, [], density_sources),
+    OUT_MASK: (SRC_MASK, [], mask_sources),
+}
 
 
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    srcs = density_sources() if out == OUT_DENSITY else sources()
-    return any(os.path.getmtime(s) > t for s in srcs)
+    return any(os.path.getmtime(s) > t for s in JOBS[out][2]())
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the three libraries side by side).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the four libraries side by side).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, src, extra in ((OUT, SRC, []), (OUT_EXP, SRC, ["-DKSA_EXPERIMENTS"]), (OUT_DENSITY, SRC_DENSITY, [])):
+    for out, (src, extra, _) in JOBS.items():
         if not force and not is_stale(out):
             continue
         cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]

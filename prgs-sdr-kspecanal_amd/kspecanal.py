@@ -16,7 +16,12 @@ onto fftSize points and transformed once; default 0 = off), `pfbSpectra` (K >= 1
 spectrometer -- a block of (P+K-1)*fftSize samples holds K such spectra, summed as power, a density; default 0 = off),
 `density` (L:lo:hi, zeroSpan only: a density / persistence histogram of every frame's dB spectrum, L levels over [lo, hi) dB
 against the waterfall's columns, handed off as d['density'], d['densityNaN'], d['densityEdges'], d['densityRows'];
-default empty = off) and `densitySave` (a file that takes the [L+1, W] int64 counts, NaN row last, with np.save).
+default empty = off), `densitySave` (a file that takes the [L+1, W] int64 counts, NaN row last, with np.save),
+`mask` (flat:U[:L] | file:PATH | learn:F:M, optionally :minBins=K and :events=E, zeroSpan only: a frequency-mask trigger --
+every frame's dB spectrum is compared against an upper and a lower limit line, the frames that cross are reported and every
+bin counts its crossings; handed off as d['maskEvents'], d['maskEventsTotal'], d['maskHits'], d['maskRows'],
+d['maskEventRows']; default empty = off) and `maskSave` (an .npz of events, events_total, hits, rows_seen, upper, lower and
+event_rows, the dB spectra of the stored events).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -39,6 +44,7 @@ from . import engine as _engine
 from .engine import SpectrumEngine, KsaError, FMT_C64, FMT_U8
 from . import sources
 from .density import SpectrumDensity
+from .mask import SpectrumMask, learn_mask, EVENT_DTYPE, MAX_CAPACITY
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -68,7 +74,7 @@ _KEYS = {
     # additive keys of this build
     "SOURCE": ("source", str), "DEVICE": ("device", int), "IQFORMAT": ("iqFormat", str.lower),
     "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int), "PFBSPECTRA": ("pfbSpectra", int),
-    "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str),
+    "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str), "MASK": ("mask", str), "MASKSAVE": ("maskSave", str),
 }
 
 
@@ -84,7 +90,7 @@ def defaults():
         "bGrid": True, "bUsePSD": False, "bScanRangeBaseDataIsRaw": False,
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
-        "density": "", "densitySave": "",
+        "density": "", "densitySave": "", "mask": "", "maskSave": "",
     }
 
 
@@ -166,6 +172,7 @@ def handle_args(d, argv=None):
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] needs bUsePSD false: the PSD diagnostic is per block".format(d["frameBatch"]))
     _handle_pfb(d)
     _handle_density(d)
+    _handle_mask(d)
     return d
 
 
@@ -195,6 +202,86 @@ def _handle_density(d):
     if d["bUsePSD"]:
         prg_quit(d, "ERROR:handle_args: density [{}] needs bUsePSD false: it counts the engine's own dB rows".format(text))
     d["density.spec"] = (levels, lo, hi)
+
+
+MASK_RULE = ("mask wants flat:U[:L] (dB, L <= U), file:PATH (an .npy of [fftSize] or [2][fftSize] values, upper then lower, no NaN, "
+             "lower <= upper) or learn:F:M (the first F >= 1 frames plus M dB), optionally followed by :minBins=K (1..fftSize) "
+             "and :events=E (1..%d)" % MAX_CAPACITY)
+
+
+def _handle_mask(d):
+    """mask flat:U[:L] | file:PATH | learn:F:M, with optional :minBins=K and :events=E (additive, zeroSpan only):
+    d['mask.spec'] = dict(kind, upper, lower, frames, margin, min_bins, capacity), or None when the key is off."""
+    d["mask.spec"] = None
+    text = d["mask"]
+    if not text:
+        if d["maskSave"]:
+            print("WARN:handle_args: maskSave [{}] is ignored without mask".format(d["maskSave"]))
+        return
+
+    def refuse():
+        prg_quit(d, "ERROR:handle_args: mask [{}]: {}".format(text, MASK_RULE))
+
+    n = d["fftSize"]
+    spec = dict(kind=None, upper=None, lower=None, frames=0, margin=0.0, min_bins=1, capacity=4096)
+    body = text
+    try:
+        seen = set()
+        while True:                                  # the optional suffixes, in either order, each at most once
+            head, sep, last = body.rpartition(":")
+            name, eq, value = last.partition("=")
+            key = {"minbins": "min_bins", "events": "capacity"}.get(name.lower())
+            if not sep or not eq or key is None:
+                break
+            if key in seen:
+                raise ValueError(text)
+            seen.add(key)
+            spec[key] = int(value)
+            body = head
+        kind, _, rest = body.partition(":")
+        spec["kind"] = kind = kind.lower()
+        if kind == "flat":
+            vals = [float(v) for v in rest.split(":")]
+            if len(vals) not in (1, 2) or any(np.isnan(v) for v in vals) or (len(vals) == 2 and vals[1] > vals[0]):
+                raise ValueError(text)
+            spec["upper"] = np.full(n, vals[0], dtype=np.float32)
+            spec["lower"] = np.full(n, vals[1], dtype=np.float32) if len(vals) == 2 else None
+        elif kind == "file":
+            if not rest:
+                raise ValueError(text)
+            spec["path"] = rest
+        elif kind == "learn":
+            frames, margin = rest.split(":")
+            spec["frames"], spec["margin"] = int(frames), float(margin)
+            if spec["frames"] < 1 or not np.isfinite(spec["margin"]):
+                raise ValueError(text)
+        else:
+            raise ValueError(text)
+        if not (1 <= spec["min_bins"] <= n and 1 <= spec["capacity"] <= MAX_CAPACITY):
+            raise ValueError(text)
+    except ValueError:
+        refuse()
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: mask [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: mask [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: mask [{}] needs bUsePSD false: it checks the engine's own dB rows".format(text))
+    if kind == "file":
+        try:
+            a = np.asarray(np.load(spec["path"], allow_pickle=False), dtype=np.float32)
+        except (OSError, ValueError, TypeError):
+            refuse()
+        if a.shape == (n,):
+            spec["upper"] = a
+        elif a.shape == (2, n):
+            spec["upper"], spec["lower"] = np.ascontiguousarray(a[0]), np.ascontiguousarray(a[1])
+        else:
+            refuse()
+        if np.isnan(a).any() or (spec["lower"] is not None and np.any(spec["lower"] > spec["upper"])):
+            refuse()
+    d["mask.spec"] = spec
 
 
 def _handle_pfb(d):
@@ -693,19 +780,93 @@ def zero_span(d):
     dens = None
     if spec is not None:                         # its columns are the waterfall's
         dens = SpectrumDensity(d["fftSize"], eng.hm_width, spec[0], spec[1], spec[2], device=d["device"])
+    mspec = d.get("mask.spec") if sdr_curscan is _gpu_curscan else None
+    trig = _MaskFeed(d, mspec) if mspec is not None else None
     try:
-        if batch > 1 or dens is not None:        # the density is fed by the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens)
+        if batch > 1 or dens is not None or trig is not None:    # density and mask are fed by the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens, trig)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
             _density_handoff(d, dens)
+        if trig is not None:
+            trig.handoff(d)
     finally:
         if dens is not None:
             dens.close()
+        if trig is not None:
+            trig.close()
     if _materialize(d, eng)["frames"] == 0:      # full-width arrays once, for SaveSigLvls and whoever called main()
         for k in ("Fft.Max", "Fft.Min", "Fft.Avg", "Fft.Cur"):
             d[k] = None                          # no frame ran: the curves are still None (K:427-430)
+
+
+class _MaskFeed:
+    """The mask key's state over a run: the SpectrumMask (made at once for flat / file, after the first F frames for learn),
+    the rows being learnt from, and the dB spectra of the stored events, picked from each batch's rows as the events arrive."""
+
+    def __init__(self, d, spec):
+        self.spec, self.n, self.device = spec, d["fftSize"], d["device"]
+        self.mask, self.learnt, self.frames_done = None, [], 0
+        self.event_rows, self.stored = [], 0
+        if spec["kind"] != "learn":
+            self._make(spec["upper"], spec["lower"])
+
+    def _make(self, upper, lower):
+        self.mask = SpectrumMask(self.n, upper, lower, min_bins=self.spec["min_bins"], capacity=self.spec["capacity"],
+                                 device=self.device)
+
+    def feed(self, db):
+        """db: float32 [k][fftSize], the dB rows of frames frames_done .. frames_done + k of the run."""
+        first = self.frames_done
+        self.frames_done += len(db)
+        if self.mask is None:                        # learn:F:M -- the boundary may fall inside a batch
+            take = min(len(db), self.spec["frames"] - first)
+            self.learnt.append(np.array(db[:take], dtype=np.float32))
+            if first + take < self.spec["frames"]:
+                return
+            self._make(learn_mask(np.concatenate(self.learnt), self.spec["margin"]), None)
+            self.mask.set_row_base(self.spec["frames"])  # row numbers are frame numbers of the run
+            self.learnt = []
+            db, first = db[take:], first + take
+        if not len(db):
+            return
+        self.mask.check_rows(db)
+        if self.stored < self.mask.capacity:
+            ev, _ = self.mask.events()
+            for row in ev["row"][self.stored:]:
+                self.event_rows.append(np.array(db[row - first], dtype=np.float32))
+            self.stored = len(ev)
+
+    def handoff(self, d):
+        """The hand-off arrays, the INFO line, maskSave."""
+        n = self.n
+        rows_arr = np.array(self.event_rows, dtype=np.float32).reshape(-1, n)
+        if self.mask is None:
+            print("WARN:zero_span: mask learn wanted [{}] frames, the run had [{}]: nothing was checked".format(
+                self.spec["frames"], self.frames_done))
+            ev, total, hits, rows = np.zeros(0, dtype=EVENT_DTYPE), 0, np.zeros((3, n), dtype=np.int64), 0
+            upper, lower = np.full(n, np.inf, dtype=np.float32), np.full(n, -np.inf, dtype=np.float32)
+            busiest, share = -1, 0.0
+        else:
+            ev, total = self.mask.events()
+            hits, rows = self.mask.hits()
+            upper = self.mask.upper
+            lower = np.full(n, -np.inf, dtype=np.float32) if self.mask.lower is None else self.mask.lower
+            occ = self.mask.occupancy()
+            busiest = int(np.argmax(occ))
+            share = float(occ[busiest])
+        d["maskEvents"], d["maskEventsTotal"], d["maskHits"], d["maskRows"], d["maskEventRows"] = ev, total, hits, rows, rows_arr
+        print("INFO:zero_span: mask rows [{}], events stored [{}] / total [{}], highest occupancy [{:.6f}] at bin [{}]".format(
+            rows, len(ev), total, share, busiest))
+        if d["maskSave"]:
+            with open(d["maskSave"], "wb") as f:
+                np.savez(f, events=ev, events_total=np.int64(total), hits=hits, rows_seen=np.int64(rows), upper=upper,
+                         lower=lower, event_rows=rows_arr)
+
+    def close(self):
+        if self.mask is not None:
+            self.mask.close()
 
 
 def _density_handoff(d, dens):
@@ -749,12 +910,13 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None):
+def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
     frames, and a source that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of
-    frameBatch 1.  With a density object every batch also returns its frames' dB rows, which the object counts."""
+    frameBatch 1.  With a density object every batch also returns its frames' dB rows, which the object counts; with a mask
+    they are checked against its lines (both may be on: they consume the same rows)."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
     full = d["fullSize"]
     dtype, per = raw_dtype(u8)
@@ -779,10 +941,14 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None):
                         got += 1
                 except EOFError:
                     pass
-            if got and dens is None:
+            if got and dens is None and trig is None:
                 eng.frames(blocks[:got])                                     # K:464-484 for the whole batch, one call
             elif got:
-                dens.add_rows(eng.frames(blocks[:got], cur_db=True)[0])
+                db = eng.frames(blocks[:got], cur_db=True)[0]
+                if dens is not None:
+                    dens.add_rows(db)
+                if trig is not None:
+                    trig.feed(db)
             done += got
             if got < k:
                 prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)
