@@ -2,8 +2,8 @@
 the .so sits next to this file so that it travels to the GPU box with the repo snapshot.
 Beside it libksa_exp.so, the same sources with -DKSA_EXPERIMENTS: the only build that reads the KSA_* environment
 switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel through it); the package never loads it.
-And libksa_density.so and libksa_mask.so, the companion libraries of include/ksa_density.h and include/ksa_mask.h, each from
-its own sources under csrc_density/ and csrc_mask/."""
+And libksa_density.so, libksa_mask.so and libksa_ddc.so, the companion libraries of include/ksa_density.h, include/ksa_mask.h
+and include/ksa_ddc.h, each from its own sources under csrc_density/, csrc_mask/ and csrc_ddc/."""
 import os
 import shutil
 import subprocess
@@ -17,6 +17,8 @@ SRC_DENSITY = os.path.join(HERE, "csrc_density", "ksd_api.hip")
 OUT_DENSITY = os.path.join(HERE, "libksa_density.so")
 SRC_MASK = os.path.join(HERE, "csrc_mask", "ksm_api.hip")
 OUT_MASK = os.path.join(HERE, "libksa_mask.so")
+SRC_DDC = os.path.join(HERE, "csrc_ddc", "kdc_api.hip")
+OUT_DDC = os.path.join(HERE, "libksa_ddc.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
@@ -38,12 +40,17 @@ def mask_sources():
     return _tree("csrc_mask", "ksa_mask.h")
 
 
+def ddc_sources():
+    return _tree("csrc_ddc", "ksa_ddc.h")
+
+
 # product -> (the .hip that is compiled, extra flags, every file the product depends on)
 JOBS = {
     OUT: (SRC, [], sources),
     OUT_EXP: (SRC, ["-DKSA_EXPERIMENTS"], sources),
     OUT_DENSITY: (SRC_DENSITY, [], density_sources),
     OUT_MASK: (SRC_MASK, [], mask_sources),
+    OUT_DDC: (SRC_DDC, [], ddc_sources),
 }
 
 
@@ -55,7 +62,7 @@ def is_stale(out=OUT):
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the four libraries side by side).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the five libraries side by side).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
     for out, (src, extra, _) in JOBS.items():

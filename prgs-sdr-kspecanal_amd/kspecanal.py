@@ -20,8 +20,11 @@ default empty = off), `densitySave` (a file that takes the [L+1, W] int64 counts
 `mask` (flat:U[:L] | file:PATH | learn:F:M, optionally :minBins=K and :events=E, zeroSpan only: a frequency-mask trigger --
 every frame's dB spectrum is compared against an upper and a lower limit line, the frames that cross are reported and every
 bin counts its crossings; handed off as d['maskEvents'], d['maskEventsTotal'], d['maskHits'], d['maskRows'],
-d['maskEventRows']; default empty = off) and `maskSave` (an .npz of events, events_total, hits, rows_seen, upper, lower and
-event_rows, the dB spectra of the stored events).
+d['maskEventRows']; default empty = off), `maskSave` (an .npz of events, events_total, hits, rows_seen, upper, lower and
+event_rows, the dB spectra of the stored events) and `zoom` (D[:offsetHz[:tapsPerPhase]], zeroSpan only: a digital
+down-converter in front of the engine -- every frame captures D*(fullSize-1) + D*tapsPerPhase samples, which are mixed down by
+offsetHz, low-pass filtered and decimated by D on the GPU, so that the same fftSize spans samplingRate/D around
+centerFreq + offsetHz; default empty = off).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -41,10 +44,11 @@ import time
 import numpy as np
 
 from . import engine as _engine
-from .engine import SpectrumEngine, KsaError, FMT_C64, FMT_U8
+from .engine import SpectrumEngine, KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
 from . import sources
 from .density import SpectrumDensity
 from .mask import SpectrumMask, learn_mask, EVENT_DTYPE, MAX_CAPACITY
+from .ddc import DownConverter, ddc_lowpass, MAX_DECIM, MAX_TAPS, MAX_IN
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -75,6 +79,7 @@ _KEYS = {
     "SOURCE": ("source", str), "DEVICE": ("device", int), "IQFORMAT": ("iqFormat", str.lower),
     "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int), "PFBSPECTRA": ("pfbSpectra", int),
     "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str), "MASK": ("mask", str), "MASKSAVE": ("maskSave", str),
+    "ZOOM": ("zoom", str),
 }
 
 
@@ -90,7 +95,7 @@ def defaults():
         "bGrid": True, "bUsePSD": False, "bScanRangeBaseDataIsRaw": False,
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
-        "density": "", "densitySave": "", "mask": "", "maskSave": "",
+        "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
     }
 
 
@@ -173,6 +178,7 @@ def handle_args(d, argv=None):
     _handle_pfb(d)
     _handle_density(d)
     _handle_mask(d)
+    _handle_zoom(d)
     return d
 
 
@@ -284,6 +290,47 @@ def _handle_mask(d):
     d["mask.spec"] = spec
 
 
+ZOOM_RULE = ("zoom wants D[:offsetHz[:tapsPerPhase]] with an integer 1 <= D <= %d, a finite |offsetHz| <= samplingRate/2 and an "
+             "integer 1 <= tapsPerPhase <= 16 with D x tapsPerPhase <= %d (defaults: offsetHz 0, tapsPerPhase 8); a batch of "
+             "D x (fullSize - 1) + D x tapsPerPhase samples per frame must stay below 2^28 samples" % (MAX_DECIM, MAX_TAPS))
+
+
+def _handle_zoom(d):
+    """zoom D[:offsetHz[:tapsPerPhase]] (additive, zeroSpan only): the digital down-converter in front of the engine.
+    d['zoom.spec'] = dict(decim, offset, taps_per_phase, ntaps, block_len, center, span), or None when the key is off; startFreq
+    and endFreq become those of the zoomed span."""
+    d["zoom.spec"] = None
+    text = d["zoom"]
+    if not text:
+        return
+    try:
+        parts = text.split(":")
+        if not 1 <= len(parts) <= 3:
+            raise ValueError(text)
+        decim = int(parts[0])
+        offset = float(parts[1]) if len(parts) > 1 else 0.0
+        tpp = int(parts[2]) if len(parts) > 2 else 8
+        if not (1 <= decim <= MAX_DECIM and np.isfinite(offset) and abs(offset) <= d["samplingRate"] / 2
+                and 1 <= tpp <= 16 and decim * tpp <= MAX_TAPS):
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: zoom [{}]: {}".format(text, ZOOM_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: zoom [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: zoom [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: zoom [{}] needs bUsePSD false: the PSD diagnostic sees the whole band".format(text))
+    ntaps = decim * tpp
+    block_len = decim * (d["fullSize"] - 1) + ntaps
+    if d["frameBatch"] * block_len > MAX_IN:
+        prg_quit(d, "ERROR:handle_args: zoom [{}]: {}".format(text, ZOOM_RULE))
+    center, span = d["centerFreq"] + offset, d["samplingRate"] / decim
+    d["zoom.spec"] = dict(decim=decim, offset=offset, taps_per_phase=tpp, ntaps=ntaps, block_len=block_len, center=center, span=span)
+    d["startFreq"], d["endFreq"] = center - span / 2, center + span / 2
+
+
 def _handle_pfb(d):
     """pfbTaps P (additive): the polyphase front end.  fullSize becomes P*fftSize (P segments of fftSize samples per
     spectrum), `window` names the taper of the prototype; the within-block overlap and fold have nothing left to do.
@@ -335,6 +382,10 @@ def print_info(d):
     elif d["pfbTaps"]:
         print("INFO: pfbTaps [{}]: fullSize[{}] = pfbTaps x fftSize, prototype sinc x window[{}]".format(
             d["pfbTaps"], d["fullSize"], d["window"]))
+    if d.get("zoom.spec"):
+        z = d["zoom.spec"]
+        print("INFO: zoom [{}]: span [{}] Hz around [{}] Hz, bin width [{}] Hz, low-pass of [{}] taps, [{}] samples per frame".format(
+            z["decim"], z["span"], z["center"], z["span"] / d["fftSize"], z["ntaps"], z["block_len"]))
 
 
 # ------------------------------------------------------------------------------------------ SDR seam
@@ -766,7 +817,11 @@ def zero_span(d):
     d["timeWasStr"] = None
     if d.get("sdr") is not None:
         d["sdr"], _ = sdr_setup(d["sdr"], d["centerFreq"], d["samplingRate"], d["gain"])
-    freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], 1 / d["samplingRate"]) + d["centerFreq"])   # K:444-445
+    zoom = d.get("zoom.spec") if sdr_curscan is _gpu_curscan else None
+    if zoom is not None:                         # the zoomed span: the decimated rate around the mixer's frequency
+        freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], zoom["decim"] / d["samplingRate"]) + zoom["center"])
+    else:
+        freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], 1 / d["samplingRate"]) + d["centerFreq"])   # K:444-445
     d["freqs"] = freqs
     print("ZeroSpan: min[{}] max[{}]".format(min(freqs), max(freqs)))
     batch = d["frameBatch"]
@@ -783,8 +838,8 @@ def zero_span(d):
     mspec = d.get("mask.spec") if sdr_curscan is _gpu_curscan else None
     trig = _MaskFeed(d, mspec) if mspec is not None else None
     try:
-        if batch > 1 or dens is not None or trig is not None:    # density and mask are fed by the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig)
+        if batch > 1 or dens is not None or trig is not None or zoom is not None:    # density, mask and zoom run the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
@@ -910,16 +965,24 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None):
+def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
     frames, and a source that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of
     frameBatch 1.  With a density object every batch also returns its frames' dB rows, which the object counts; with a mask
-    they are checked against its lines (both may be on: they consume the same rows)."""
+    they are checked against its lines (both may be on: they consume the same rows).  With zoom every block is
+    D x (fullSize - 1) + T raw samples: the down-converter reads the batch from the page-locked buffer (kdc_blocks_dev) and the
+    engine takes its fullSize complex64 outputs per block from device memory (ksa_frames_dev), the dB rows coming back through
+    page-locked memory as on the int8 / int16 route."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
-    full = d["fullSize"]
+    full = d["fullSize"] if zoom is None else zoom["block_len"]
     dtype, per = raw_dtype(u8)
+    ddc = None
+    if zoom is not None:
+        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[u8]
+        ddc = DownConverter(fmt, zoom["decim"], ddc_lowpass(zoom["decim"], zoom["taps_per_phase"]), freq=zoom["offset"],
+                            sampling_rate=d["samplingRate"], max_in=batch * full, device=d["device"])
     stage = _engine.PinnedBuffer((batch, per * full), dtype)
     blocks = stage.array
     read_blocks = getattr(d["sdr"], "read_blocks", None)
@@ -941,7 +1004,16 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None):
                         got += 1
                 except EOFError:
                     pass
-            if got and dens is None and trig is None:
+            if got and ddc is not None:
+                ddc.blocks_dev(blocks, got, full)                            # [got][fullSize] complex64 in its own buffer
+                db = eng._pinned_out("db", (got, d["fftSize"])) if dens is not None or trig is not None else None
+                eng.frames_dev(ddc.out_ptr, FMT_C64, got, cur_db=db)
+                eng.synchronize()
+                if dens is not None:
+                    dens.add_rows(db)
+                if trig is not None:
+                    trig.feed(db)
+            elif got and dens is None and trig is None:
                 eng.frames(blocks[:got])                                     # K:464-484 for the whole batch, one call
             elif got:
                 db = eng.frames(blocks[:got], cur_db=True)[0]
@@ -956,6 +1028,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None):
                 break
             _handoff(d, eng, freqs, new_rows=min(got, _engine.HM_ROWS))     # once per batch: the batch's newest rows
     finally:
+        if ddc is not None:
+            ddc.close()
         stage.close()
 
 
