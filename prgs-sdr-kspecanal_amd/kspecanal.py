@@ -24,7 +24,12 @@ d['maskEventRows']; default empty = off), `maskSave` (an .npz of events, events_
 event_rows, the dB spectra of the stored events) and `zoom` (D[:offsetHz[:tapsPerPhase]], zeroSpan only: a digital
 down-converter in front of the engine -- every frame captures D*(fullSize-1) + D*tapsPerPhase samples, which are mixed down by
 offsetHz, low-pass filtered and decimated by D on the GPU, so that the same fftSize spans samplingRate/D around
-centerFreq + offsetHz; default empty = off).
+centerFreq + offsetHz; default empty = off) and `detect` (T:G:THR[:mode=ca|go|so][:minWidth=W][:maxGap=K][:events=E],
+zeroSpan only: a CFAR signal detector -- every bin of every frame's dB spectrum is compared against the mean of T training cells
+on either side beyond G guard cells plus THR dB, the detected bins are grouped into emissions (start bin, stop bin, peak, floor)
+and every bin counts the frames in which it lay inside one; handed off as d['detectEmissions'], d['detectEmissionsTotal'],
+d['detectHits'], d['detectRows']; default empty = off), `detectSave` (an .npz of emissions, emissions_total, hits, rows_seen, the
+parameters, and every emission's centre and width in Hz).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -49,6 +54,8 @@ from . import sources
 from .density import SpectrumDensity
 from .mask import SpectrumMask, learn_mask, EVENT_DTYPE, MAX_CAPACITY
 from .ddc import DownConverter, ddc_lowpass, MAX_DECIM, MAX_TAPS, MAX_IN
+from . import detect as _detect
+from .detect import SignalDetector, emission_freqs
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -79,7 +86,7 @@ _KEYS = {
     "SOURCE": ("source", str), "DEVICE": ("device", int), "IQFORMAT": ("iqFormat", str.lower),
     "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int), "PFBSPECTRA": ("pfbSpectra", int),
     "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str), "MASK": ("mask", str), "MASKSAVE": ("maskSave", str),
-    "ZOOM": ("zoom", str),
+    "ZOOM": ("zoom", str), "DETECT": ("detect", str), "DETECTSAVE": ("detectSave", str),
 }
 
 
@@ -96,6 +103,7 @@ def defaults():
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
+        "detect": "", "detectSave": "",
     }
 
 
@@ -179,6 +187,7 @@ def handle_args(d, argv=None):
     _handle_density(d)
     _handle_mask(d)
     _handle_zoom(d)
+    _handle_detect(d)
     return d
 
 
@@ -329,6 +338,53 @@ def _handle_zoom(d):
     center, span = d["centerFreq"] + offset, d["samplingRate"] / decim
     d["zoom.spec"] = dict(decim=decim, offset=offset, taps_per_phase=tpp, ntaps=ntaps, block_len=block_len, center=center, span=span)
     d["startFreq"], d["endFreq"] = center - span / 2, center + span / 2
+
+
+DETECT_RULE = ("detect wants T:G:THR with integers 1 <= T <= %d training and 0 <= G <= %d guard cells on either side and a finite "
+               "threshold 0 <= THR <= 100 in dB, optionally followed by :mode=ca|go|so, :minWidth=W (1..fftSize), :maxGap=K (0..%d) "
+               "and :events=E (1..%d), each at most once; fftSize %d..%d" % (
+                   _detect.MAX_TRAIN, _detect.MAX_GUARD, _detect.MAX_GAP, _detect.MAX_CAPACITY, _detect.MIN_NBINS, _detect.MAX_NBINS))
+
+
+def _handle_detect(d):
+    """detect T:G:THR[:mode=ca|go|so][:minWidth=W][:maxGap=K][:events=E] (additive, zeroSpan only): d['detect.spec'] =
+    dict(train, guard, threshold, mode, min_width, max_gap, capacity), or None when the key is off."""
+    d["detect.spec"] = None
+    text = d["detect"]
+    if not text:
+        if d["detectSave"]:
+            print("WARN:handle_args: detectSave [{}] is ignored without detect".format(d["detectSave"]))
+        return
+    n = d["fftSize"]
+    spec = dict(train=0, guard=0, threshold=0.0, mode="ca", min_width=1, max_gap=0, capacity=4096)
+    try:
+        parts = text.split(":")
+        if len(parts) < 3:
+            raise ValueError(text)
+        spec["train"], spec["guard"], spec["threshold"] = int(parts[0]), int(parts[1]), float(parts[2])
+        seen = set()
+        for part in parts[3:]:                       # the optional suffixes, in any order, each at most once
+            name, eq, value = part.partition("=")
+            key = {"mode": "mode", "minwidth": "min_width", "maxgap": "max_gap", "events": "capacity"}.get(name.lower())
+            if not eq or key is None or key in seen:
+                raise ValueError(text)
+            seen.add(key)
+            spec[key] = value.lower() if key == "mode" else int(value)
+        if not (1 <= spec["train"] <= _detect.MAX_TRAIN and 0 <= spec["guard"] <= _detect.MAX_GUARD
+                and np.isfinite(spec["threshold"]) and 0 <= spec["threshold"] <= 100 and spec["mode"] in _detect.MODES
+                and 1 <= spec["min_width"] <= n and 0 <= spec["max_gap"] <= _detect.MAX_GAP
+                and 1 <= spec["capacity"] <= _detect.MAX_CAPACITY and _detect.MIN_NBINS <= n <= _detect.MAX_NBINS):
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: detect [{}]: {}".format(text, DETECT_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: detect [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: detect [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: detect [{}] needs bUsePSD false: it reads the engine's own dB rows".format(text))
+    d["detect.spec"] = spec
 
 
 def _handle_pfb(d):
@@ -837,20 +893,26 @@ def zero_span(d):
         dens = SpectrumDensity(d["fftSize"], eng.hm_width, spec[0], spec[1], spec[2], device=d["device"])
     mspec = d.get("mask.spec") if sdr_curscan is _gpu_curscan else None
     trig = _MaskFeed(d, mspec) if mspec is not None else None
+    dspec = d.get("detect.spec") if sdr_curscan is _gpu_curscan else None
+    det = _DetectFeed(d, dspec) if dspec is not None else None
     try:
-        if batch > 1 or dens is not None or trig is not None or zoom is not None:    # density, mask and zoom run the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom)
+        if batch > 1 or dens is not None or trig is not None or zoom is not None or det is not None:    # density, mask, zoom and detect run the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
             _density_handoff(d, dens)
         if trig is not None:
             trig.handoff(d)
+        if det is not None:
+            det.handoff(d, freqs)
     finally:
         if dens is not None:
             dens.close()
         if trig is not None:
             trig.close()
+        if det is not None:
+            det.close()
     if _materialize(d, eng)["frames"] == 0:      # full-width arrays once, for SaveSigLvls and whoever called main()
         for k in ("Fft.Max", "Fft.Min", "Fft.Avg", "Fft.Cur"):
             d[k] = None                          # no frame ran: the curves are still None (K:427-430)
@@ -924,6 +986,42 @@ class _MaskFeed:
             self.mask.close()
 
 
+class _DetectFeed:
+    """The detect key's state over a run: the SignalDetector, fed every batch's dB rows; row numbers are frame numbers."""
+
+    def __init__(self, d, spec):
+        self.spec = spec
+        self.det = SignalDetector(d["fftSize"], spec["train"], spec["guard"], spec["threshold"], mode=spec["mode"],
+                                  min_width=spec["min_width"], max_gap=spec["max_gap"], capacity=spec["capacity"],
+                                  device=d["device"])
+
+    def feed(self, db):
+        """db: float32 [k][fftSize], the dB rows of the run's next k frames."""
+        if len(db):
+            self.det.detect_rows(db)
+
+    def handoff(self, d, freqs):
+        """The hand-off arrays, the INFO line, detectSave."""
+        ev, total = self.det.emissions()
+        hits, rows = self.det.hits()
+        occ = self.det.occupancy()
+        busiest = int(np.argmax(occ))
+        d["detectEmissions"], d["detectEmissionsTotal"], d["detectHits"], d["detectRows"] = ev, total, hits, rows
+        print("INFO:zero_span: detect rows [{}], emissions stored [{}] / total [{}], highest occupancy [{:.6f}] at bin [{}]".format(
+            rows, len(ev), total, float(occ[busiest]), busiest))
+        if d["detectSave"]:
+            center, width = emission_freqs(ev, freqs)
+            s = self.spec
+            with open(d["detectSave"], "wb") as f:
+                np.savez(f, emissions=ev, emissions_total=np.int64(total), hits=hits, rows_seen=np.int64(rows),
+                         train=np.int32(s["train"]), guard=np.int32(s["guard"]), threshold_db=np.float32(s["threshold"]),
+                         mode=np.array(s["mode"]), min_width=np.int32(s["min_width"]), max_gap=np.int32(s["max_gap"]),
+                         center_hz=center, width_hz=width)
+
+    def close(self):
+        self.det.close()
+
+
 def _density_handoff(d, dens):
     """The density's hand-off arrays (drawing the bitmap is the caller's: density.image), the INFO line, densitySave."""
     counts, rows = dens.read()
@@ -965,13 +1063,14 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None):
+def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
     frames, and a source that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of
     frameBatch 1.  With a density object every batch also returns its frames' dB rows, which the object counts; with a mask
-    they are checked against its lines (both may be on: they consume the same rows).  With zoom every block is
+    they are checked against its lines, with a detector they are searched for emissions (all may be on: they consume the same
+    rows).  With zoom every block is
     D x (fullSize - 1) + T raw samples: the down-converter reads the batch from the page-locked buffer (kdc_blocks_dev) and the
     engine takes its fullSize complex64 outputs per block from device memory (ksa_frames_dev), the dB rows coming back through
     page-locked memory as on the int8 / int16 route."""
@@ -1006,14 +1105,16 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None):
                     pass
             if got and ddc is not None:
                 ddc.blocks_dev(blocks, got, full)                            # [got][fullSize] complex64 in its own buffer
-                db = eng._pinned_out("db", (got, d["fftSize"])) if dens is not None or trig is not None else None
+                db = eng._pinned_out("db", (got, d["fftSize"])) if dens is not None or trig is not None or det is not None else None
                 eng.frames_dev(ddc.out_ptr, FMT_C64, got, cur_db=db)
                 eng.synchronize()
                 if dens is not None:
                     dens.add_rows(db)
                 if trig is not None:
                     trig.feed(db)
-            elif got and dens is None and trig is None:
+                if det is not None:
+                    det.feed(db)
+            elif got and dens is None and trig is None and det is None:
                 eng.frames(blocks[:got])                                     # K:464-484 for the whole batch, one call
             elif got:
                 db = eng.frames(blocks[:got], cur_db=True)[0]
@@ -1021,6 +1122,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None):
                     dens.add_rows(db)
                 if trig is not None:
                     trig.feed(db)
+                if det is not None:
+                    det.feed(db)
             done += got
             if got < k:
                 prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)
