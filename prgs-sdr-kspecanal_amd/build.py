@@ -4,7 +4,8 @@ Beside it libksa_exp.so, the same sources with -DKSA_EXPERIMENTS: the only build
 switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel through it); the package never loads it.
 And libksa_density.so, libksa_mask.so and libksa_ddc.so, the companion libraries of include/ksa_density.h, include/ksa_mask.h
 and include/ksa_ddc.h, each from its own sources under csrc_density/, csrc_mask/ and csrc_ddc/.
-And libksa_detect.so, the CFAR signal detector of include/ksa_detect.h, from csrc_detect/."""
+And libksa_detect.so, the CFAR signal detector of include/ksa_detect.h, from csrc_detect/.
+And libksa_demod.so, the AM / FM / PM demodulator of include/ksa_demod.h, from csrc_demod/."""
 import os
 import shutil
 import subprocess
@@ -22,6 +23,8 @@ SRC_DDC = os.path.join(HERE, "csrc_ddc", "kdc_api.hip")
 OUT_DDC = os.path.join(HERE, "libksa_ddc.so")
 SRC_DETECT = os.path.join(HERE, "csrc_detect", "kse_api.hip")
 OUT_DETECT = os.path.join(HERE, "libksa_detect.so")
+SRC_DEMOD = os.path.join(HERE, "csrc_demod", "kdm_api.hip")
+OUT_DEMOD = os.path.join(HERE, "libksa_demod.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
@@ -51,6 +54,10 @@ def detect_sources():
     return _tree("csrc_detect", "ksa_detect.h")
 
 
+def demod_sources():
+    return _tree("csrc_demod", "ksa_demod.h")
+
+
 # product -> (the .hip that is compiled, extra flags, every file the product depends on)
 JOBS = {
     OUT: (SRC, [], sources),
@@ -59,6 +66,7 @@ JOBS = {
     OUT_MASK: (SRC_MASK, [], mask_sources),
     OUT_DDC: (SRC_DDC, [], ddc_sources),
     OUT_DETECT: (SRC_DETECT, [], detect_sources),
+    OUT_DEMOD: (SRC_DEMOD, [], demod_sources),
 }
 
 
@@ -70,7 +78,7 @@ def is_stale(out=OUT):
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the six libraries side by side).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the seven libraries side by side).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
     for out, (src, extra, _) in JOBS.items():

@@ -29,7 +29,12 @@ zeroSpan only: a CFAR signal detector -- every bin of every frame's dB spectrum 
 on either side beyond G guard cells plus THR dB, the detected bins are grouped into emissions (start bin, stop bin, peak, floor)
 and every bin counts the frames in which it lay inside one; handed off as d['detectEmissions'], d['detectEmissionsTotal'],
 d['detectHits'], d['detectRows']; default empty = off), `detectSave` (an .npz of emissions, emissions_total, hits, rows_seen, the
-parameters, and every emission's centre and width in Hz).
+parameters, and every emission's centre and width in Hz), `demod` (MODE[:audioDecim[:tapsPerPhase[:deemphUs]]] with MODE
+am|fm|pm, zeroSpan only, needs `zoom` (`zoom 1` passes the whole band): an AM / FM / PM demodulator behind the zoom -- every
+frame's zoomed block is turned into amplitude, frequency or phase versus time, low-pass filtered and decimated by audioDecim on
+the GPU into int16 PCM; each block is demodulated on its own and the blocks abut in the hand-off and in the file; handed off as
+d['demodAudio'] (int16) and d['demodRate']; default empty = off) and `demodSave` (FILE.wav, a mono 16-bit WAV file of that
+audio at samplingRate / (zoom D x audioDecim), rounded to an integer).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -56,6 +61,8 @@ from .mask import SpectrumMask, learn_mask, EVENT_DTYPE, MAX_CAPACITY
 from .ddc import DownConverter, ddc_lowpass, MAX_DECIM, MAX_TAPS, MAX_IN
 from . import detect as _detect
 from .detect import SignalDetector, emission_freqs
+from . import demod as _demod
+from .demod import Demodulator, demod_taps, write_wav
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -87,6 +94,7 @@ _KEYS = {
     "FRAMEBATCH": ("frameBatch", int), "PFBTAPS": ("pfbTaps", int), "PFBSPECTRA": ("pfbSpectra", int),
     "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str), "MASK": ("mask", str), "MASKSAVE": ("maskSave", str),
     "ZOOM": ("zoom", str), "DETECT": ("detect", str), "DETECTSAVE": ("detectSave", str),
+    "DEMOD": ("demod", str), "DEMODSAVE": ("demodSave", str),
 }
 
 
@@ -103,7 +111,7 @@ def defaults():
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
-        "detect": "", "detectSave": "",
+        "detect": "", "detectSave": "", "demod": "", "demodSave": "",
     }
 
 
@@ -188,6 +196,7 @@ def handle_args(d, argv=None):
     _handle_mask(d)
     _handle_zoom(d)
     _handle_detect(d)
+    _handle_demod(d)
     return d
 
 
@@ -387,6 +396,54 @@ def _handle_detect(d):
     d["detect.spec"] = spec
 
 
+DEMOD_PCM_SCALE = 32767.0                    # int16 per unit of the filtered detector: AM full scale 1, FM and PM one cycle
+DEMOD_RULE = ("demod wants MODE[:audioDecim[:tapsPerPhase[:deemphUs]]] with MODE am|fm|pm, an integer 1 <= audioDecim <= %d, an "
+              "integer tapsPerPhase >= 1 with audioDecim x tapsPerPhase <= %d and a finite deemphUs > 0 (defaults: audioDecim 1, "
+              "tapsPerPhase 8, no de-emphasis); it needs zoom (zoom 1 passes the whole band) and a fullSize above "
+              "audioDecim x tapsPerPhase" % (_demod.MAX_DECIM, _demod.MAX_TAPS))
+
+
+def _handle_demod(d):
+    """demod MODE[:audioDecim[:tapsPerPhase[:deemphUs]]] (additive, zeroSpan only, behind zoom): d['demod.spec'] =
+    dict(mode, decim, taps_per_phase, ntaps, deemph_us, out_per_block, rate), or None when the key is off."""
+    d["demod.spec"] = None
+    text = d["demod"]
+    if not text:
+        if d["demodSave"]:
+            print("WARN:handle_args: demodSave [{}] is ignored without demod".format(d["demodSave"]))
+        return
+    try:
+        parts = text.split(":")
+        if not 1 <= len(parts) <= 4:
+            raise ValueError(text)
+        mode = parts[0].lower()
+        decim = int(parts[1]) if len(parts) > 1 else 1
+        tpp = int(parts[2]) if len(parts) > 2 else 8
+        deemph = float(parts[3]) if len(parts) > 3 else None
+        if not (mode in _demod.MODES and 1 <= decim <= _demod.MAX_DECIM and tpp >= 1 and decim * tpp <= _demod.MAX_TAPS
+                and (deemph is None or (np.isfinite(deemph) and deemph > 0))):
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: demod [{}]: {}".format(text, DEMOD_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: demod [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: demod [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: demod [{}] needs bUsePSD false: the PSD diagnostic sees the whole band".format(text))
+    ntaps = decim * tpp
+    lead = 1 if mode == "fm" else 0
+    if d["zoom.spec"] is None or d["fullSize"] < ntaps + lead:
+        prg_quit(d, "ERROR:handle_args: demod [{}]: {}".format(text, DEMOD_RULE))
+    exact = d["samplingRate"] / (d["zoom.spec"]["decim"] * decim)
+    rate = int(round(exact))
+    if rate != exact:
+        print("WARN:handle_args: demod [{}]: the audio rate [{}] is not an integer, the WAV file says [{}]".format(text, exact, rate))
+    d["demod.spec"] = dict(mode=mode, decim=decim, taps_per_phase=tpp, ntaps=ntaps, deemph_us=deemph,
+                           out_per_block=(d["fullSize"] - lead - ntaps) // decim + 1, rate=rate)
+
+
 def _handle_pfb(d):
     """pfbTaps P (additive): the polyphase front end.  fullSize becomes P*fftSize (P segments of fftSize samples per
     spectrum), `window` names the taper of the prototype; the within-block overlap and fold have nothing left to do.
@@ -442,6 +499,11 @@ def print_info(d):
         z = d["zoom.spec"]
         print("INFO: zoom [{}]: span [{}] Hz around [{}] Hz, bin width [{}] Hz, low-pass of [{}] taps, [{}] samples per frame".format(
             z["decim"], z["span"], z["center"], z["span"] / d["fftSize"], z["ntaps"], z["block_len"]))
+    if d.get("demod.spec"):
+        m = d["demod.spec"]
+        print("INFO: demod [{}]: audio decimation [{}], low-pass of [{}] taps, de-emphasis [{}] us, [{}] samples per block at [{}] Hz; "
+              "each block is demodulated on its own and the blocks abut".format(
+                  m["mode"], m["decim"], m["ntaps"], m["deemph_us"], m["out_per_block"], m["rate"]))
 
 
 # ------------------------------------------------------------------------------------------ SDR seam
@@ -895,9 +957,11 @@ def zero_span(d):
     trig = _MaskFeed(d, mspec) if mspec is not None else None
     dspec = d.get("detect.spec") if sdr_curscan is _gpu_curscan else None
     det = _DetectFeed(d, dspec) if dspec is not None else None
+    aspec = d.get("demod.spec") if zoom is not None else None
+    audio = _DemodFeed(d, aspec, zoom, batch) if aspec is not None else None
     try:
         if batch > 1 or dens is not None or trig is not None or zoom is not None or det is not None:    # density, mask, zoom and detect run the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det)
+            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
@@ -906,7 +970,11 @@ def zero_span(d):
             trig.handoff(d)
         if det is not None:
             det.handoff(d, freqs)
+        if audio is not None:
+            audio.handoff(d)
     finally:
+        if audio is not None:
+            audio.close()
         if dens is not None:
             dens.close()
         if trig is not None:
@@ -1022,6 +1090,37 @@ class _DetectFeed:
         self.det.close()
 
 
+class _DemodFeed:
+    """The demod key's state over a run: the Demodulator behind the down-converter, fed every batch's zoomed blocks in device
+    memory; each block is demodulated on its own and the blocks abut in the audio."""
+
+    def __init__(self, d, spec, zoom, batch):
+        self.spec, self.full = spec, d["fullSize"]
+        fs = d["samplingRate"] / zoom["decim"]
+        taps = demod_taps(spec["decim"], spec["taps_per_phase"], deemph_us=spec["deemph_us"],
+                          sampling_rate=fs if spec["deemph_us"] is not None else None, dc_block=spec["mode"] == "am")
+        self.dem = Demodulator(spec["mode"], spec["decim"], taps, out_fmt="s16", pcm_scale=DEMOD_PCM_SCALE,
+                               max_in=batch * self.full, device=d["device"])
+        self.parts = []
+
+    def feed(self, iq_dev, got):
+        """iq_dev: [got][fullSize] complex64 in device memory, the down-converter's own buffer."""
+        m = self.dem.blocks_dev(iq_dev, got, self.full)
+        self.parts.append(self.dem.read_out(got * m))
+
+    def handoff(self, d):
+        """The hand-off array, the INFO line, demodSave."""
+        pcm = np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=np.int16)
+        d["demodAudio"], d["demodRate"] = pcm, self.spec["rate"]
+        print("INFO:zero_span: demod [{}]: [{}] samples at [{}] Hz, [{}] per block, peak [{}]".format(
+            self.spec["mode"], len(pcm), self.spec["rate"], self.spec["out_per_block"], int(np.abs(pcm.astype(np.int32)).max()) if len(pcm) else 0))
+        if d["demodSave"]:
+            write_wav(d["demodSave"], pcm, self.spec["rate"])
+
+    def close(self):
+        self.dem.close()
+
+
 def _density_handoff(d, dens):
     """The density's hand-off arrays (drawing the bitmap is the caller's: density.image), the INFO line, densitySave."""
     counts, rows = dens.read()
@@ -1063,7 +1162,7 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None):
+def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
@@ -1073,7 +1172,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
     rows).  With zoom every block is
     D x (fullSize - 1) + T raw samples: the down-converter reads the batch from the page-locked buffer (kdc_blocks_dev) and the
     engine takes its fullSize complex64 outputs per block from device memory (ksa_frames_dev), the dB rows coming back through
-    page-locked memory as on the int8 / int16 route."""
+    page-locked memory as on the int8 / int16 route.  With demod the demodulator's block form runs over the same zoomed blocks
+    (kdm_blocks_dev) and the batch's int16 audio is fetched with kdm_read_out."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
     full = d["fullSize"] if zoom is None else zoom["block_len"]
     dtype, per = raw_dtype(u8)
@@ -1108,6 +1208,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
                 db = eng._pinned_out("db", (got, d["fftSize"])) if dens is not None or trig is not None or det is not None else None
                 eng.frames_dev(ddc.out_ptr, FMT_C64, got, cur_db=db)
                 eng.synchronize()
+                if audio is not None:
+                    audio.feed(ddc.out_ptr, got)
                 if dens is not None:
                     dens.add_rows(db)
                 if trig is not None:
