@@ -5,7 +5,8 @@ switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel
 And libksa_density.so, libksa_mask.so and libksa_ddc.so, the companion libraries of include/ksa_density.h, include/ksa_mask.h
 and include/ksa_ddc.h, each from its own sources under csrc_density/, csrc_mask/ and csrc_ddc/.
 And libksa_detect.so, the CFAR signal detector of include/ksa_detect.h, from csrc_detect/.
-And libksa_demod.so, the AM / FM / PM demodulator of include/ksa_demod.h, from csrc_demod/."""
+And libksa_demod.so, the AM / FM / PM demodulator of include/ksa_demod.h, from csrc_demod/.
+And libksa_chan.so, the polyphase channelizer of include/ksa_chan.h, from csrc_chan/."""
 import os
 import shutil
 import subprocess
@@ -25,6 +26,8 @@ SRC_DETECT = os.path.join(HERE, "csrc_detect", "kse_api.hip")
 OUT_DETECT = os.path.join(HERE, "libksa_detect.so")
 SRC_DEMOD = os.path.join(HERE, "csrc_demod", "kdm_api.hip")
 OUT_DEMOD = os.path.join(HERE, "libksa_demod.so")
+SRC_CHAN = os.path.join(HERE, "csrc_chan", "kch_api.hip")
+OUT_CHAN = os.path.join(HERE, "libksa_chan.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
@@ -58,6 +61,10 @@ def demod_sources():
     return _tree("csrc_demod", "ksa_demod.h")
 
 
+def chan_sources():
+    return _tree("csrc_chan", "ksa_chan.h")
+
+
 # product -> (the .hip that is compiled, extra flags, every file the product depends on)
 JOBS = {
     OUT: (SRC, [], sources),
@@ -67,6 +74,7 @@ JOBS = {
     OUT_DDC: (SRC_DDC, [], ddc_sources),
     OUT_DETECT: (SRC_DETECT, [], detect_sources),
     OUT_DEMOD: (SRC_DEMOD, [], demod_sources),
+    OUT_CHAN: (SRC_CHAN, [], chan_sources),
 }
 
 
@@ -78,7 +86,7 @@ def is_stale(out=OUT):
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the seven libraries side by side).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the eight libraries side by side).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
     for out, (src, extra, _) in JOBS.items():

@@ -34,7 +34,11 @@ am|fm|pm, zeroSpan only, needs `zoom` (`zoom 1` passes the whole band): an AM / 
 frame's zoomed block is turned into amplitude, frequency or phase versus time, low-pass filtered and decimated by audioDecim on
 the GPU into int16 PCM; each block is demodulated on its own and the blocks abut in the hand-off and in the file; handed off as
 d['demodAudio'] (int16) and d['demodRate']; default empty = off) and `demodSave` (FILE.wav, a mono 16-bit WAV file of that
-audio at samplingRate / (zoom D x audioDecim), rounded to an integer).
+audio at samplingRate / (zoom D x audioDecim), rounded to an integer), `channels` (M[:O[:tapsPerBranch[:pick]]], zeroSpan only,
+instead of `zoom`: a polyphase channelizer in front of the engine -- every frame's capture becomes all M channels of the band at
+once, each at samplingRate x O / M, channel `pick` goes on to the engine (and to `demod`, which it satisfies in place of
+`zoom`), and the mean power of every channel over the run is handed off as d['channelsPower'] in dB with d['channelsFreqs'];
+default empty = off) and `channelsSave` (an .npz of power_db, freqs and the parameters).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -63,6 +67,8 @@ from . import detect as _detect
 from .detect import SignalDetector, emission_freqs
 from . import demod as _demod
 from .demod import Demodulator, demod_taps, write_wav
+from . import chan as _chan
+from .chan import Channelizer, chan_prototype, channel_freqs
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -95,6 +101,7 @@ _KEYS = {
     "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str), "MASK": ("mask", str), "MASKSAVE": ("maskSave", str),
     "ZOOM": ("zoom", str), "DETECT": ("detect", str), "DETECTSAVE": ("detectSave", str),
     "DEMOD": ("demod", str), "DEMODSAVE": ("demodSave", str),
+    "CHANNELS": ("channels", str), "CHANNELSSAVE": ("channelsSave", str),
 }
 
 
@@ -111,7 +118,7 @@ def defaults():
         "zeroSpanSaveFile": "/tmp/zerospan.save", "zeroSpanPlayFile": "/tmp/zerospan.save",
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
-        "detect": "", "detectSave": "", "demod": "", "demodSave": "",
+        "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
     }
 
 
@@ -195,6 +202,7 @@ def handle_args(d, argv=None):
     _handle_density(d)
     _handle_mask(d)
     _handle_zoom(d)
+    _handle_channels(d)
     _handle_detect(d)
     _handle_demod(d)
     return d
@@ -349,6 +357,57 @@ def _handle_zoom(d):
     d["startFreq"], d["endFreq"] = center - span / 2, center + span / 2
 
 
+CHANNELS_RULE = ("channels wants M[:O[:tapsPerBranch[:pick]]] with M a power of two %d <= M <= %d, O 1, 2 or 4 with O <= M, an "
+                 "integer 1 <= tapsPerBranch <= %d with M x tapsPerBranch <= %d and a channel 0 <= pick < M (defaults: O 2, "
+                 "tapsPerBranch 8, pick 0); a batch of (M / O) x (ceil((M x tapsPerBranch - 1) / (M / O)) + fullSize - 1) + 1 samples "
+                 "per frame must stay below 2^28 samples" % (_chan.MIN_CHAN, _chan.MAX_CHAN, _chan.MAX_BRANCH_TAPS, _chan.MAX_TAPS))
+
+
+def _handle_channels(d):
+    """channels M[:O[:tapsPerBranch[:pick]]] (additive, zeroSpan only, instead of zoom): the polyphase channelizer in front of
+    the engine.  d['chan.spec'] = dict(nchan, oversample, taps_per_branch, pick, decim, ntaps, first, block_len, offset, center,
+    span), or None when the key is off; startFreq and endFreq become those of the picked channel."""
+    d["chan.spec"] = None
+    text = d["channels"]
+    if not text:
+        if d["channelsSave"]:
+            print("WARN:handle_args: channelsSave [{}] is ignored without channels".format(d["channelsSave"]))
+        return
+    try:
+        parts = text.split(":")
+        if not 1 <= len(parts) <= 4:
+            raise ValueError(text)
+        nchan = int(parts[0])
+        over = int(parts[1]) if len(parts) > 1 else 2
+        tpb = int(parts[2]) if len(parts) > 2 else 8
+        pick = int(parts[3]) if len(parts) > 3 else 0
+        if not (_chan.MIN_CHAN <= nchan <= _chan.MAX_CHAN and nchan & (nchan - 1) == 0 and over in (1, 2, 4) and over <= nchan
+                and 1 <= tpb <= _chan.MAX_BRANCH_TAPS and nchan * tpb <= _chan.MAX_TAPS and 0 <= pick < nchan):
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: channels [{}]: {}".format(text, CHANNELS_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: channels [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: channels [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: channels [{}] needs bUsePSD false: the PSD diagnostic sees the whole band".format(text))
+    if d["zoom.spec"] is not None:
+        prg_quit(d, "ERROR:handle_args: channels [{}] and zoom [{}] exclude each other: either is the front end of the engine".format(
+            text, d["zoom"]))
+    decim, ntaps = nchan // over, nchan * tpb
+    first = -(-(ntaps - 1) // decim)
+    block_len = decim * (first + d["fullSize"] - 1) + 1
+    if d["frameBatch"] * block_len > _chan.MAX_IN:
+        prg_quit(d, "ERROR:handle_args: channels [{}]: {}".format(text, CHANNELS_RULE))
+    offset = float(channel_freqs(nchan, d["samplingRate"])[pick])
+    center, span = d["centerFreq"] + offset, d["samplingRate"] / decim
+    d["chan.spec"] = dict(nchan=nchan, oversample=over, taps_per_branch=tpb, pick=pick, decim=decim, ntaps=ntaps, first=first,
+                          block_len=block_len, offset=offset, center=center, span=span)
+    d["startFreq"], d["endFreq"] = center - span / 2, center + span / 2
+
+
 DETECT_RULE = ("detect wants T:G:THR with integers 1 <= T <= %d training and 0 <= G <= %d guard cells on either side and a finite "
                "threshold 0 <= THR <= 100 in dB, optionally followed by :mode=ca|go|so, :minWidth=W (1..fftSize), :maxGap=K (0..%d) "
                "and :events=E (1..%d), each at most once; fftSize %d..%d" % (
@@ -434,9 +493,10 @@ def _handle_demod(d):
         prg_quit(d, "ERROR:handle_args: demod [{}] needs bUsePSD false: the PSD diagnostic sees the whole band".format(text))
     ntaps = decim * tpp
     lead = 1 if mode == "fm" else 0
-    if d["zoom.spec"] is None or d["fullSize"] < ntaps + lead:
+    front = d["zoom.spec"] if d["zoom.spec"] is not None else d["chan.spec"]       # channels stands in for zoom
+    if front is None or d["fullSize"] < ntaps + lead:
         prg_quit(d, "ERROR:handle_args: demod [{}]: {}".format(text, DEMOD_RULE))
-    exact = d["samplingRate"] / (d["zoom.spec"]["decim"] * decim)
+    exact = d["samplingRate"] / (front["decim"] * decim)
     rate = int(round(exact))
     if rate != exact:
         print("WARN:handle_args: demod [{}]: the audio rate [{}] is not an integer, the WAV file says [{}]".format(text, exact, rate))
@@ -499,6 +559,11 @@ def print_info(d):
         z = d["zoom.spec"]
         print("INFO: zoom [{}]: span [{}] Hz around [{}] Hz, bin width [{}] Hz, low-pass of [{}] taps, [{}] samples per frame".format(
             z["decim"], z["span"], z["center"], z["span"] / d["fftSize"], z["ntaps"], z["block_len"]))
+    if d.get("chan.spec"):
+        c = d["chan.spec"]
+        print("INFO: channels [{}]: oversampling [{}], prototype of [{}] taps, channel [{}]: span [{}] Hz around [{}] Hz, bin width [{}] Hz, "
+              "[{}] samples per frame".format(c["nchan"], c["oversample"], c["ntaps"], c["pick"], c["span"], c["center"],
+                                              c["span"] / d["fftSize"], c["block_len"]))
     if d.get("demod.spec"):
         m = d["demod.spec"]
         print("INFO: demod [{}]: audio decimation [{}], low-pass of [{}] taps, de-emphasis [{}] us, [{}] samples per block at [{}] Hz; "
@@ -936,8 +1001,10 @@ def zero_span(d):
     if d.get("sdr") is not None:
         d["sdr"], _ = sdr_setup(d["sdr"], d["centerFreq"], d["samplingRate"], d["gain"])
     zoom = d.get("zoom.spec") if sdr_curscan is _gpu_curscan else None
-    if zoom is not None:                         # the zoomed span: the decimated rate around the mixer's frequency
-        freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], zoom["decim"] / d["samplingRate"]) + zoom["center"])
+    cspec = d.get("chan.spec") if sdr_curscan is _gpu_curscan else None
+    front = zoom if zoom is not None else cspec  # either front end: the decimated rate around its centre
+    if front is not None:                        # the zoomed span: the decimated rate around the mixer's frequency
+        freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], front["decim"] / d["samplingRate"]) + front["center"])
     else:
         freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], 1 / d["samplingRate"]) + d["centerFreq"])   # K:444-445
     d["freqs"] = freqs
@@ -957,11 +1024,12 @@ def zero_span(d):
     trig = _MaskFeed(d, mspec) if mspec is not None else None
     dspec = d.get("detect.spec") if sdr_curscan is _gpu_curscan else None
     det = _DetectFeed(d, dspec) if dspec is not None else None
-    aspec = d.get("demod.spec") if zoom is not None else None
-    audio = _DemodFeed(d, aspec, zoom, batch) if aspec is not None else None
+    aspec = d.get("demod.spec") if front is not None else None
+    audio = _DemodFeed(d, aspec, front, batch) if aspec is not None else None
+    bank = _ChanFeed(d, cspec, batch) if cspec is not None else None
     try:
-        if batch > 1 or dens is not None or trig is not None or zoom is not None or det is not None:    # density, mask, zoom and detect run the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio)
+        if batch > 1 or dens is not None or trig is not None or front is not None or det is not None:    # density, mask, zoom and detect run the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
@@ -972,9 +1040,13 @@ def zero_span(d):
             det.handoff(d, freqs)
         if audio is not None:
             audio.handoff(d)
+        if bank is not None:
+            bank.handoff(d)
     finally:
         if audio is not None:
             audio.close()
+        if bank is not None:
+            bank.close()
         if dens is not None:
             dens.close()
         if trig is not None:
@@ -1103,9 +1175,10 @@ class _DemodFeed:
                                max_in=batch * self.full, device=d["device"])
         self.parts = []
 
-    def feed(self, iq_dev, got):
-        """iq_dev: [got][fullSize] complex64 in device memory, the down-converter's own buffer."""
-        m = self.dem.blocks_dev(iq_dev, got, self.full)
+    def feed(self, iq_dev, got, stride=None):
+        """iq_dev: [got][fullSize] complex64 in device memory, the down-converter's own buffer (or, with a stride in values,
+        one channel of every block of the channelizer's)."""
+        m = self.dem.blocks_dev(iq_dev, got, self.full, block_stride=stride)
         self.parts.append(self.dem.read_out(got * m))
 
     def handoff(self, d):
@@ -1119,6 +1192,45 @@ class _DemodFeed:
 
     def close(self):
         self.dem.close()
+
+
+class _ChanFeed:
+    """The channels key's state over a run: the Channelizer in front of the engine, fed every batch's raw blocks; the picked
+    channel of every block goes on as a strided view of its buffer, and every channel's power is summed over the run."""
+
+    def __init__(self, d, spec, batch):
+        self.spec, self.full = spec, d["fullSize"]
+        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
+        self.bank = Channelizer(fmt, spec["nchan"], spec["oversample"], chan_prototype(spec["nchan"], spec["taps_per_branch"]),
+                                max_in=batch * spec["block_len"], device=d["device"])
+        self.power, self.values = np.zeros(spec["nchan"], dtype=np.float64), 0
+
+    def run(self, blocks, got):
+        """(address, stride in values) of the picked channel of every block: [got][M][fullSize] complex64 in the bank's buffer."""
+        cols = self.bank.blocks_dev(blocks, got, self.spec["block_len"])
+        assert cols == self.full
+        self.power += self.bank.channel_power(0, cols)
+        self.values += got * cols
+        return self.bank.out_ptr + 8 * self.spec["pick"] * cols, self.spec["nchan"] * cols
+
+    def handoff(self, d):
+        """The hand-off arrays, the INFO line, channelsSave."""
+        s = self.spec
+        with np.errstate(divide="ignore"):
+            db = 10 * np.log10(self.power / max(self.values, 1))
+        freqs = channel_freqs(s["nchan"], d["samplingRate"], d["centerFreq"])
+        d["channelsPower"], d["channelsFreqs"] = db, freqs
+        top = np.argsort(-db, kind="stable")[:3]
+        print("INFO:zero_span: channels [{}]: [{}] values per channel, strongest {}".format(
+            s["nchan"], self.values, ", ".join("[{}] at [{}] Hz [{:.2f}] dB".format(int(c), freqs[c], db[c]) for c in top)))
+        if d["channelsSave"]:
+            with open(d["channelsSave"], "wb") as f:
+                np.savez(f, power_db=db, freqs=freqs, nchan=s["nchan"], oversample=s["oversample"],
+                         taps_per_branch=s["taps_per_branch"], pick=s["pick"], values=self.values,
+                         sampling_rate=d["samplingRate"], center_freq=d["centerFreq"])
+
+    def close(self):
+        self.bank.close()
 
 
 def _density_handoff(d, dens):
@@ -1162,7 +1274,7 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None):
+def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None, bank=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
@@ -1173,9 +1285,11 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
     D x (fullSize - 1) + T raw samples: the down-converter reads the batch from the page-locked buffer (kdc_blocks_dev) and the
     engine takes its fullSize complex64 outputs per block from device memory (ksa_frames_dev), the dB rows coming back through
     page-locked memory as on the int8 / int16 route.  With demod the demodulator's block form runs over the same zoomed blocks
-    (kdm_blocks_dev) and the batch's int16 audio is fetched with kdm_read_out."""
+    (kdm_blocks_dev) and the batch's int16 audio is fetched with kdm_read_out.  With channels in place of zoom every block is
+    the channelizer's block length, kch_blocks_dev leaves [got][M][fullSize] complex64 in its buffer, and the engine and the
+    demodulator read the picked channel of every block at a stride of M x fullSize values."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
-    full = d["fullSize"] if zoom is None else zoom["block_len"]
+    full = zoom["block_len"] if zoom is not None else bank.spec["block_len"] if bank is not None else d["fullSize"]
     dtype, per = raw_dtype(u8)
     ddc = None
     if zoom is not None:
@@ -1203,13 +1317,17 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
                         got += 1
                 except EOFError:
                     pass
-            if got and ddc is not None:
-                ddc.blocks_dev(blocks, got, full)                            # [got][fullSize] complex64 in its own buffer
+            if got and (ddc is not None or bank is not None):
+                if ddc is not None:
+                    ddc.blocks_dev(blocks, got, full)                        # [got][fullSize] complex64 in its own buffer
+                    src, stride = ddc.out_ptr, None
+                else:
+                    src, stride = bank.run(blocks, got)                      # one channel of [got][M][fullSize]
                 db = eng._pinned_out("db", (got, d["fftSize"])) if dens is not None or trig is not None or det is not None else None
-                eng.frames_dev(ddc.out_ptr, FMT_C64, got, cur_db=db)
+                eng.frames_dev(src, FMT_C64, got, cur_db=db, frame_stride=stride)
                 eng.synchronize()
                 if audio is not None:
-                    audio.feed(ddc.out_ptr, got)
+                    audio.feed(src, got, stride)
                 if dens is not None:
                     dens.add_rows(db)
                 if trig is not None:
