@@ -1,0 +1,82 @@
+"""What the bindings of the six companion libraries (density, mask, ddc, detect, demod, chan) share: loading a library with its
+ABI check and signatures, and the lifetime, stream and kernel_info methods of the class over it.  _lib.py binds libksa.so on
+its own (it loads eagerly); there is no fallback here either: a missing library raises."""
+import ctypes as C
+import os
+
+from . import _lib
+from ._lib import KsaError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+class Binding:
+    """One companion library: its file beside this module, the prefix of its symbols ("kdc_"), the ABI version the binding
+    expects and name -> (restype, argtypes) for every symbol its header declares."""
+
+    def __init__(self, file_name, prefix, abi_version, signatures):
+        self.file_name, self.prefix, self.abi_version, self.signatures = file_name, prefix, abi_version, signatures
+        self.path = os.path.join(HERE, file_name)
+        self._loaded = None
+
+    def load(self, path=None):
+        path = self.path if path is None else path
+        _lib._preload_torch_hip_runtime()      # every library binds the one HIP runtime torch mapped
+        if not os.path.exists(path):
+            raise KsaError("%s is missing at %s -- build it with `python __graft_entry__.py` "
+                           "(hipcc --offload-arch=gfx950); there is no CPU fallback" % (self.file_name, path))
+        lib = C.CDLL(path)
+        abi = getattr(lib, self.prefix + "abi_version")
+        abi.restype = C.c_int
+        if abi() != self.abi_version:          # checked first: a stale build is named as such, not as a missing symbol
+            raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
+                           % (path, abi(), self.abi_version))
+        for name, (res, args) in self.signatures.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        return lib
+
+    def lib(self):
+        """The library, loaded on first use (the spectrum engine alone does not need it)."""
+        if self._loaded is None:
+            self._loaded = self.load()
+        return self._loaded
+
+    def check(self, rc):
+        if rc != 0:
+            raise KsaError(getattr(self.lib(), self.prefix + "last_error")().decode("utf-8", "replace"))
+
+
+class Companion:
+    """Base of the six wrapper classes.  A subclass sets _binding and _info_fields (what k??_kernel_info reports after the
+    handle, in order) and its constructor leaves the library's handle in _h."""
+    _binding = None
+    _info_fields = ()
+    _h = None
+
+    def _call(self, name, *args):
+        self._binding.check(getattr(self._binding.lib(), self._binding.prefix + name)(self._h, *args))
+
+    def close(self):
+        if self._h:
+            getattr(self._binding.lib(), self._binding.prefix + "destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream):
+        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
+        self._call("set_stream", C.c_void_p(stream or 0))
+
+    def synchronize(self):
+        self._call("synchronize")
+
+    def kernel_info(self):
+        v = [C.c_int32() for _ in self._info_fields]
+        self._call("kernel_info", *[C.byref(x) for x in v])
+        return dict(zip(self._info_fields, [x.value for x in v]))

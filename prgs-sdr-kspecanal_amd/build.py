@@ -1,81 +1,50 @@
-"""Build libksa.so (HIP kernels + C ABI) for gfx950 with hipcc.  In-tree, no JIT cache:
-the .so sits next to this file so that it travels to the GPU box with the repo snapshot.
-Beside it libksa_exp.so, the same sources with -DKSA_EXPERIMENTS: the only build that reads the KSA_* environment
-switches (tests/test_gpu_tickets.py runs both unit orders of the spectrum kernel through it); the package never loads it.
-And libksa_density.so, libksa_mask.so and libksa_ddc.so, the companion libraries of include/ksa_density.h, include/ksa_mask.h
-and include/ksa_ddc.h, each from its own sources under csrc_density/, csrc_mask/ and csrc_ddc/.
-And libksa_detect.so, the CFAR signal detector of include/ksa_detect.h, from csrc_detect/.
-And libksa_demod.so, the AM / FM / PM demodulator of include/ksa_demod.h, from csrc_demod/.
-And libksa_chan.so, the polyphase channelizer of include/ksa_chan.h, from csrc_chan/."""
+"""Build the eight shared libraries for gfx950 with hipcc, one translation unit each (PRODUCTS below).  In-tree, no JIT cache:
+every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's sources with
+-DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
 import os
 import shutil
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "csrc", "ksa_api.hip")
-OUT = os.path.join(HERE, "libksa.so")
-OUT_EXP = os.path.join(HERE, "libksa_exp.so")
-SRC_DENSITY = os.path.join(HERE, "csrc_density", "ksd_api.hip")
-OUT_DENSITY = os.path.join(HERE, "libksa_density.so")
-SRC_MASK = os.path.join(HERE, "csrc_mask", "ksm_api.hip")
-OUT_MASK = os.path.join(HERE, "libksa_mask.so")
-SRC_DDC = os.path.join(HERE, "csrc_ddc", "kdc_api.hip")
-OUT_DDC = os.path.join(HERE, "libksa_ddc.so")
-SRC_DETECT = os.path.join(HERE, "csrc_detect", "kse_api.hip")
-OUT_DETECT = os.path.join(HERE, "libksa_detect.so")
-SRC_DEMOD = os.path.join(HERE, "csrc_demod", "kdm_api.hip")
-OUT_DEMOD = os.path.join(HERE, "libksa_demod.so")
-SRC_CHAN = os.path.join(HERE, "csrc_chan", "kch_api.hip")
-OUT_CHAN = os.path.join(HERE, "libksa_chan.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
+# product -> (source directory, the .hip that is compiled, public header under include/, extra flags)
+PRODUCTS = {
+    "libksa.so": ("csrc", "ksa_api.hip", "ksa.h", []),
+    "libksa_exp.so": ("csrc", "ksa_api.hip", "ksa.h", ["-DKSA_EXPERIMENTS"]),
+    "libksa_density.so": ("csrc_density", "ksd_api.hip", "ksa_density.h", []),
+    "libksa_mask.so": ("csrc_mask", "ksm_api.hip", "ksa_mask.h", []),
+    "libksa_ddc.so": ("csrc_ddc", "kdc_api.hip", "ksa_ddc.h", []),
+    "libksa_detect.so": ("csrc_detect", "kse_api.hip", "ksa_detect.h", []),
+    "libksa_demod.so": ("csrc_demod", "kdm_api.hip", "ksa_demod.h", []),
+    "libksa_chan.so": ("csrc_chan", "kch_api.hip", "ksa_chan.h", []),
+}
+OUT = os.path.join(HERE, "libksa.so")
+OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 
-def _tree(subdir, header):
+
+def _files(subdir):
     d = os.path.join(HERE, subdir)
-    return [os.path.join(d, f) for f in sorted(os.listdir(d))] + [os.path.join(HERE, "..", "include", header)]
+    return [os.path.join(d, f) for f in sorted(os.listdir(d))]
+
+
+def _sources(product):
+    """Every file the product depends on: its directory, its header and, for a companion library, csrc_shared/ (which csrc/
+    does not include)."""
+    subdir, _, header, _ = PRODUCTS[product]
+    shared = _files("csrc_shared") if subdir != "csrc" else []
+    return _files(subdir) + shared + [os.path.join(HERE, "..", "include", header)]
 
 
 def sources():
-    return _tree("csrc", "ksa.h")
+    return _sources("libksa.so")
 
 
-def density_sources():
-    return _tree("csrc_density", "ksa_density.h")
-
-
-def mask_sources():
-    return _tree("csrc_mask", "ksa_mask.h")
-
-
-def ddc_sources():
-    return _tree("csrc_ddc", "ksa_ddc.h")
-
-
-def detect_sources():
-    return _tree("csrc_detect", "ksa_detect.h")
-
-
-def demod_sources():
-    return _tree("csrc_demod", "ksa_demod.h")
-
-
-def chan_sources():
-    return _tree("csrc_chan", "ksa_chan.h")
-
-
-# product -> (the .hip that is compiled, extra flags, every file the product depends on)
-JOBS = {
-    OUT: (SRC, [], sources),
-    OUT_EXP: (SRC, ["-DKSA_EXPERIMENTS"], sources),
-    OUT_DENSITY: (SRC_DENSITY, [], density_sources),
-    OUT_MASK: (SRC_MASK, [], mask_sources),
-    OUT_DDC: (SRC_DDC, [], ddc_sources),
-    OUT_DETECT: (SRC_DETECT, [], detect_sources),
-    OUT_DEMOD: (SRC_DEMOD, [], demod_sources),
-    OUT_CHAN: (SRC_CHAN, [], chan_sources),
-}
+# product's path -> (the .hip that is compiled, extra flags, every file the product depends on)
+JOBS = {os.path.join(HERE, name): (os.path.join(HERE, subdir, hip), extra, lambda name=name: _sources(name))
+        for name, (subdir, hip, _, extra) in PRODUCTS.items()}
 
 
 def is_stale(out=OUT):

@@ -4,17 +4,13 @@ filtered by one prototype and decimated by D = M / O; the result is channel-majo
 Demodulator.blocks_dev (nblocks = M, block_stride = the channel stride) and the engine's frames_dev already accept.  There is no
 fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _lib
+from ._companion import Binding, Companion
 from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
-from .ddc import DevArray
-from .engine import _ptr, window_table
+from .engine import DevArray, _ptr, window_table
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libksa_chan.so")
 ABI_VERSION = 1
 MIN_CHAN, MAX_CHAN, MAX_BRANCH_TAPS, MAX_TAPS, MAX_IN = 2, 1024, 32, 8192, 2 ** 28 - 1
 FORM_LDS = 0
@@ -44,37 +40,9 @@ SIGNATURES = {
 }
 
 
-def load(path=LIB_PATH):
-    _lib._preload_torch_hip_runtime()      # every library binds the one HIP runtime torch mapped
-    if not os.path.exists(path):
-        raise KsaError("libksa_chan.so is missing at %s -- build it with `python __graft_entry__.py` "
-                       "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
-    lib = C.CDLL(path)
-    lib.kch_abi_version.restype = C.c_int
-    if lib.kch_abi_version() != ABI_VERSION:
-        raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
-                       % (path, lib.kch_abi_version(), ABI_VERSION))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-_loaded = None
-
-
-def lib():
-    """libksa_chan.so, loaded on first use (the spectrum engine alone does not need it)."""
-    global _loaded
-    if _loaded is None:
-        _loaded = load()
-    return _loaded
-
-
-def check(rc):
-    if rc != 0:
-        raise KsaError(lib().kch_last_error().decode("utf-8", "replace"))
+_bind = Binding("libksa_chan.so", "kch_", ABI_VERSION, SIGNATURES)
+LIB_PATH = _bind.path
+load, lib, check = _bind.load, _bind.lib, _bind.check
 
 
 def chan_prototype(nchan, taps_per_branch=8, cutoff=1.0, window="hamming"):
@@ -102,16 +70,16 @@ def channel_freqs(nchan, sampling_rate, center=0.0):
     return center + np.where(c < nchan // 2, c, c - nchan) * (float(sampling_rate) / nchan)
 
 
-class Channelizer:
+class Channelizer(Companion):
     """M-channel polyphase filter bank for one IQ stream on one GPU; the contract is include/ksa_chan.h.
     out_stride is the row stride of the STREAM form in the object's own buffer, ceil(max_in / D) + 1, fixed at construction.
     After blocks_dev into the own buffer the rows lie J apart (what blocks_dev returned): layout() and `out` follow the last
     call, out_stride does not."""
+    _binding, _info_fields = _bind, ("threads", "lds_bytes", "vgprs", "grid", "tile_cols", "form")
 
     def __init__(self, fmt, nchan, oversample, taps, max_in=1 << 20, device=0, stream=None, u8_offset=127.5, u8_scale=127.5):
         self.fmt, self.nchan, self.oversample = int(fmt), int(nchan), int(oversample)
         self.device, self.max_in = int(device), int(max_in)
-        self._h = None
         self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         self.ntaps = int(self.taps.size)
         if self.nchan < 1 or self.ntaps < 1 or self.ntaps % self.nchan:
@@ -128,30 +96,6 @@ class Channelizer:
         self._out, self.out_stride, self.out_capacity = p.value, stride.value, cap.value
         if stream is not None:
             self.set_stream(stream)
-
-    # -- lifetime ---------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().kch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream):
-        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
-        check(lib().kch_set_stream(self._h, C.c_void_p(stream or 0)))
-
-    def synchronize(self):
-        check(lib().kch_synchronize(self._h))
-
-    def kernel_info(self):
-        v = [C.c_int32() for _ in range(6)]
-        check(lib().kch_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("threads", "lds_bytes", "vgprs", "grid", "tile_cols", "form"), [x.value for x in v]))
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):
@@ -246,7 +190,7 @@ class Channelizer:
         """The object's own buffer as the last call laid it out, complex64 [rows][row_stride] (stream form:
         [nchan][out_stride]), for torch.as_tensor."""
         rows, stride = self.layout()
-        return DevArray(self._out, (rows, stride), self)
+        return DevArray(self._out, (rows, stride), self, "<c8")
 
     @property
     def out_ptr(self):

@@ -3,43 +3,17 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 #include <vector>
 
 #include "../../include/ksa_chan.h"
 #include "kch_kernels.hpp"
+#include "../csrc_shared/ksa_host.hpp"
+
+static_assert(KCH_FMT_C64 == ksa::iq::FMT_C64 && KCH_FMT_U8 == ksa::iq::FMT_U8 && KCH_FMT_S8 == ksa::iq::FMT_S8 &&
+              KCH_FMT_S16 == ksa::iq::FMT_S16, "the formats of the header are the kernels' and iq_sample_bytes's");
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return 1;
-}
-
-#define HIP_OK(call)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (call);                                                               \
-    if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-// Entry points run on their object's device and hand the caller's current device back on every exit path.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 constexpr int LDS_TWO = 80 * 1024, LDS_ONE = 160 * 1024;   // two workgroups per CU, or one
 constexpr int WORK_VALUES = 8192;                          // W * M at most: 64 KiB of workspace
@@ -93,17 +67,6 @@ const void* history_fn(int fmt) {
   }
 }
 
-int check_taps(int T, const float* taps) {
-  if (!taps) return fail("null taps pointer");
-  for (int k = 0; k < T; ++k)
-    if (!std::isfinite(taps[k])) return fail("tap %d is not finite", k);
-  return 0;
-}
-
-int sample_bytes(int fmt) { return fmt == KCH_FMT_C64 ? 8 : fmt == KCH_FMT_S16 ? 4 : 2; }
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 struct kch_chan {
@@ -129,8 +92,7 @@ namespace {
 
 void free_all(kch_chan* h) {
   if (h->ev_stream) (void)hipEventDestroy(h->ev_stream);
-  for (void* p : {(void*)h->taps, (void*)h->tw, (void*)h->hist[0], (void*)h->hist[1], (void*)h->out, (void*)h->power, (void*)h->stage})
-    if (p) (void)hipFree(p);
+  free_device({h->taps, h->tw, h->hist[0], h->hist[1], h->out, h->power, h->stage});
   delete h;
 }
 
@@ -195,10 +157,9 @@ int check_stream_args(kch_chan* h, const void* iq, int64_t n_in, int64_t* ncol) 
   if (n_in < 0) return fail("n_in %lld must be >= 0", (long long)n_in);
   if (n_in > h->max_in) return fail("n_in %lld exceeds max_in %lld", (long long)n_in, h->max_in);
   if (n_in > 0 && !iq) return fail("null input pointer");
-  if (reinterpret_cast<uintptr_t>(iq) % (unsigned)sample_bytes(h->fmt))
-    return fail("input pointer is not aligned to the %d bytes of a sample", sample_bytes(h->fmt));
+  if (int rc = check_iq_aligned(iq, iq_sample_bytes(h->fmt))) return rc;
   if (h->lost) return fail("the stream state was lost when an earlier call failed after its filter launch; kch_reset starts a new stream");
-  *ncol = ceil_div(h->n_in + n_in, h->D) - ceil_div(h->n_in, h->D);
+  *ncol = stream_outputs(h->n_in, n_in, h->D);
   return 0;
 }
 
@@ -256,10 +217,7 @@ int kch_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
   if (nchan >= 4) tw[(size_t)(nchan / 4)] = make_float2(0.f, 1.f);
   int rc = 0;
   do {
-    if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->cus < 1) {
-      rc = fail("hipDeviceGetAttribute(MultiprocessorCount) failed on device %d", device);
-      break;
-    }
+    if ((rc = cu_count(device, &h->cus))) break;
     const size_t hist_bytes = (size_t)(T - 1) * 8;            // T >= 2
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->taps), (size_t)T * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->tw), (size_t)ntw * 8);
@@ -297,30 +255,19 @@ void kch_destroy(kch_chan* h) {
 
 int kch_set_stream(kch_chan* h, void* hip_stream) {
   if (!h) return fail("null channelizer object");
-  hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-  if (ns == h->stream) return 0;
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(h->device));
-  if (!h->ev_stream) HIP_OK(hipEventCreateWithFlags(&h->ev_stream, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(h->ev_stream, h->stream));
-  HIP_OK(hipStreamWaitEvent(ns, h->ev_stream, 0));
-  h->stream = ns;
-  return 0;
+  return hand_over_stream(h->device, &h->stream, &h->ev_stream, hip_stream);
 }
 
 int kch_synchronize(kch_chan* h) {
   if (!h) return fail("null channelizer object");
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  return 0;
+  return synchronize_on(h->device, h->stream);
 }
 
 int kch_out_count(kch_chan* h, int64_t n_in, int64_t* n_out) {
   if (!h) return fail("null channelizer object");
   if (!n_out) return fail("null n_out pointer");
   if (n_in < 0) return fail("n_in %lld must be >= 0", (long long)n_in);
-  *n_out = ceil_div(h->n_in + n_in, h->D) - ceil_div(h->n_in, h->D);
+  *n_out = stream_outputs(h->n_in, n_in, h->D);
   return 0;
 }
 
@@ -356,15 +303,8 @@ int kch_process(kch_chan* h, const void* iq_host, int64_t n_in, void* out_host, 
   }
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(h->device));
-  const long long bytes = (long long)n_in * sample_bytes(h->fmt);
-  if (h->stage_bytes < bytes) {
-    HIP_OK(hipStreamSynchronize(h->stream));
-    if (h->stage) (void)hipFree(h->stage);
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->stage), (size_t)bytes));
-    h->stage_bytes = bytes;
-  }
+  const long long bytes = (long long)n_in * iq_sample_bytes(h->fmt);
+  if (int rc = grow_device(&h->stage, &h->stage_bytes, bytes, h->stream)) return rc;
   HIP_OK(hipMemcpyAsync(h->stage, iq_host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
   if (int rc = stream_call(h, h->stage, n_in, h->out, h->own_stride, ncol)) return rc;
   h->rows = h->M;
@@ -388,8 +328,7 @@ int kch_blocks_dev(kch_chan* h, const void* iq_dev, int64_t block_stride, int64_
   if (block_len > h->max_in || nblocks > h->max_in / block_len)
     return fail("%lld blocks of %lld samples exceed max_in %lld", (long long)nblocks, (long long)block_len, h->max_in);
   if (nblocks > 0 && !iq_dev) return fail("null input pointer");
-  if (reinterpret_cast<uintptr_t>(iq_dev) % (unsigned)sample_bytes(h->fmt))
-    return fail("input pointer is not aligned to the %d bytes of a sample", sample_bytes(h->fmt));
+  if (int rc = check_iq_aligned(iq_dev, iq_sample_bytes(h->fmt))) return rc;
   const long long J = (block_len - 1) / h->D - first + 1;
   if (out_dev && chan_stride < J)
     return fail("chan_stride %lld is shorter than the %lld columns of a block", (long long)chan_stride, J);

@@ -3,42 +3,16 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/ksa_ddc.h"
 #include "kdc_kernels.hpp"
+#include "../csrc_shared/ksa_host.hpp"
+
+static_assert(KDC_FMT_C64 == ksa::iq::FMT_C64 && KDC_FMT_U8 == ksa::iq::FMT_U8 && KDC_FMT_S8 == ksa::iq::FMT_S8 &&
+              KDC_FMT_S16 == ksa::iq::FMT_S16, "the formats of the header are the kernels' and iq_sample_bytes's");
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return 1;
-}
-
-#define HIP_OK(call)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (call);                                                               \
-    if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-// Entry points run on their object's device and hand the caller's current device back on every exit path.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 // The tile form keeps (tile - 1) * D + T samples in LDS.  Up to SPAN_SMALL two workgroups share a CU and a thread takes as many
 // outputs (4, 2, 1) as fit; up to SPAN_LARGE one workgroup of one output per thread has the CU alone; beyond, the reduce form.
@@ -102,17 +76,6 @@ const void* history_fn(int fmt) {
   }
 }
 
-int check_taps(int T, const float* taps) {
-  if (!taps) return fail("null taps pointer");
-  for (int k = 0; k < T; ++k)
-    if (!std::isfinite(taps[k])) return fail("tap %d is not finite", k);
-  return 0;
-}
-
-int sample_bytes(int fmt) { return fmt == KDC_FMT_C64 ? 8 : fmt == KDC_FMT_S16 ? 4 : 2; }
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 struct kdc_ddc {
@@ -135,8 +98,7 @@ namespace {
 
 void free_all(kdc_ddc* h) {
   if (h->ev_stream) (void)hipEventDestroy(h->ev_stream);
-  for (void* p : {(void*)h->taps, (void*)h->hist[0], (void*)h->hist[1], (void*)h->out, (void*)h->stage})
-    if (p) (void)hipFree(p);
+  free_device({h->taps, h->hist[0], h->hist[1], h->out, h->stage});
   delete h;
 }
 
@@ -193,9 +155,8 @@ int check_stream_args(kdc_ddc* h, const void* iq, int64_t n_in, int64_t* nout) {
   if (n_in < 0) return fail("n_in %lld must be >= 0", (long long)n_in);
   if (n_in > h->max_in) return fail("n_in %lld exceeds max_in %lld", (long long)n_in, h->max_in);
   if (n_in > 0 && !iq) return fail("null input pointer");
-  if (reinterpret_cast<uintptr_t>(iq) % (unsigned)sample_bytes(h->fmt))
-    return fail("input pointer is not aligned to the %d bytes of a sample", sample_bytes(h->fmt));
-  *nout = ceil_div(h->n_in + n_in, h->D) - ceil_div(h->n_in, h->D);
+  if (int rc = check_iq_aligned(iq, iq_sample_bytes(h->fmt))) return rc;
+  *nout = stream_outputs(h->n_in, n_in, h->D);
   return 0;
 }
 
@@ -231,10 +192,7 @@ int kdc_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
   h->kernel = filter_kernel(fmt, h->plan);
   int rc = 0;
   do {
-    if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->cus < 1) {
-      rc = fail("hipDeviceGetAttribute(MultiprocessorCount) failed on device %d", device);
-      break;
-    }
+    if ((rc = cu_count(device, &h->cus))) break;
     const size_t hist_bytes = (size_t)std::max(ntaps - 1, 1) * 8;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->taps), (size_t)ntaps * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->hist[0]), hist_bytes);
@@ -266,30 +224,19 @@ void kdc_destroy(kdc_ddc* h) {
 
 int kdc_set_stream(kdc_ddc* h, void* hip_stream) {
   if (!h) return fail("null down-converter object");
-  hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-  if (ns == h->stream) return 0;
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(h->device));
-  if (!h->ev_stream) HIP_OK(hipEventCreateWithFlags(&h->ev_stream, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(h->ev_stream, h->stream));
-  HIP_OK(hipStreamWaitEvent(ns, h->ev_stream, 0));
-  h->stream = ns;
-  return 0;
+  return hand_over_stream(h->device, &h->stream, &h->ev_stream, hip_stream);
 }
 
 int kdc_synchronize(kdc_ddc* h) {
   if (!h) return fail("null down-converter object");
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  return 0;
+  return synchronize_on(h->device, h->stream);
 }
 
 int kdc_out_count(kdc_ddc* h, int64_t n_in, int64_t* n_out) {
   if (!h) return fail("null down-converter object");
   if (!n_out) return fail("null n_out pointer");
   if (n_in < 0) return fail("n_in %lld must be >= 0", (long long)n_in);
-  *n_out = ceil_div(h->n_in + n_in, h->D) - ceil_div(h->n_in, h->D);
+  *n_out = stream_outputs(h->n_in, n_in, h->D);
   return 0;
 }
 
@@ -315,15 +262,8 @@ int kdc_process(kdc_ddc* h, const void* iq_host, int64_t n_in, void* out_host, i
   if (n_in == 0) return 0;
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(h->device));
-  const long long bytes = (long long)n_in * sample_bytes(h->fmt);
-  if (h->stage_bytes < bytes) {
-    HIP_OK(hipStreamSynchronize(h->stream));
-    if (h->stage) (void)hipFree(h->stage);
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->stage), (size_t)bytes));
-    h->stage_bytes = bytes;
-  }
+  const long long bytes = (long long)n_in * iq_sample_bytes(h->fmt);
+  if (int rc = grow_device(&h->stage, &h->stage_bytes, bytes, h->stream)) return rc;
   HIP_OK(hipMemcpyAsync(h->stage, iq_host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
   if (int rc = stream_call(h, h->stage, n_in, h->out, nout)) return rc;
   if (nout > 0) HIP_OK(hipMemcpyAsync(out_host, h->out, (size_t)nout * 8, hipMemcpyDeviceToHost, h->stream));
@@ -340,8 +280,7 @@ int kdc_blocks_dev(kdc_ddc* h, const void* iq_dev, int64_t block_stride, int64_t
   if (block_len > h->max_in || nblocks > h->max_in / block_len)
     return fail("%lld blocks of %lld samples exceed max_in %lld", (long long)nblocks, (long long)block_len, h->max_in);
   if (nblocks > 0 && !iq_dev) return fail("null input pointer");
-  if (reinterpret_cast<uintptr_t>(iq_dev) % (unsigned)sample_bytes(h->fmt))
-    return fail("input pointer is not aligned to the %d bytes of a sample", sample_bytes(h->fmt));
+  if (int rc = check_iq_aligned(iq_dev, iq_sample_bytes(h->fmt))) return rc;
   const long long M = (block_len - h->T) / h->D + 1;
   if (out_dev && out_stride < M) return fail("out_stride %lld is shorter than the %lld outputs of a block", (long long)out_stride, M);
   if (!out_dev && nblocks * M > h->out_cap)

@@ -4,42 +4,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/ksa_demod.h"
 #include "kdm_kernels.hpp"
+#include "../csrc_shared/ksa_host.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return 1;
-}
-
-#define HIP_OK(call)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (call);                                                               \
-    if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-// Entry points run on their object's device and hand the caller's current device back on every exit path.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 // A tile keeps (tile - 1) * D + T floats in LDS.  The largest of 1024 (four outputs per thread) and 256 outputs whose span stays
 // within SPAN_FOUR lets four workgroups share a CU, which is what hides one workgroup's load phase behind the others' filter
@@ -90,15 +61,6 @@ const void* history_fn(int mode) {
   }
 }
 
-int check_taps(int T, const float* taps) {
-  if (!taps) return fail("null taps pointer");
-  for (int k = 0; k < T; ++k)
-    if (!std::isfinite(taps[k])) return fail("tap %d is not finite", k);
-  return 0;
-}
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 struct kdm_demod {
@@ -125,8 +87,7 @@ size_t state_bytes(const kdm_demod* h) { return (size_t)(h->T - 1 + 2) * 4; }
 
 void free_all(kdm_demod* h) {
   if (h->ev_stream) (void)hipEventDestroy(h->ev_stream);
-  for (void* p : {(void*)h->taps, (void*)h->state[0], (void*)h->state[1], h->out, (void*)h->stage})
-    if (p) (void)hipFree(p);
+  free_device({h->taps, h->state[0], h->state[1], h->out, h->stage});
   delete h;
 }
 
@@ -187,9 +148,9 @@ int check_stream_args(kdm_demod* h, const void* iq, int64_t n_in, int64_t* nout)
   if (n_in < 0) return fail("n_in %lld must be >= 0", (long long)n_in);
   if (n_in > h->max_in) return fail("n_in %lld exceeds max_in %lld", (long long)n_in, h->max_in);
   if (n_in > 0 && !iq) return fail("null input pointer");
-  if (reinterpret_cast<uintptr_t>(iq) % 8u) return fail("input pointer is not aligned to the 8 bytes of a sample");
+  if (int rc = check_iq_aligned(iq, 8)) return rc;
   if (h->lost) return fail("the stream state was lost when an earlier call failed after its filter launch; kdm_reset starts a new stream");
-  *nout = ceil_div(h->n_in + n_in, h->D) - ceil_div(h->n_in, h->D);
+  *nout = stream_outputs(h->n_in, n_in, h->D);
   return 0;
 }
 
@@ -224,10 +185,7 @@ int kdm_create(int32_t device, int32_t mode, int32_t decim, int32_t ntaps, const
   h->kernel = filter_kernel(mode, out_fmt, h->plan);
   int rc = 0;
   do {
-    if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->cus < 1) {
-      rc = fail("hipDeviceGetAttribute(MultiprocessorCount) failed on device %d", device);
-      break;
-    }
+    if ((rc = cu_count(device, &h->cus))) break;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->taps), (size_t)ntaps * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->state[0]), state_bytes(h));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->state[1]), state_bytes(h));
@@ -260,30 +218,19 @@ void kdm_destroy(kdm_demod* h) {
 
 int kdm_set_stream(kdm_demod* h, void* hip_stream) {
   if (!h) return fail("null demodulator object");
-  hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-  if (ns == h->stream) return 0;
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(h->device));
-  if (!h->ev_stream) HIP_OK(hipEventCreateWithFlags(&h->ev_stream, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(h->ev_stream, h->stream));
-  HIP_OK(hipStreamWaitEvent(ns, h->ev_stream, 0));
-  h->stream = ns;
-  return 0;
+  return hand_over_stream(h->device, &h->stream, &h->ev_stream, hip_stream);
 }
 
 int kdm_synchronize(kdm_demod* h) {
   if (!h) return fail("null demodulator object");
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  return 0;
+  return synchronize_on(h->device, h->stream);
 }
 
 int kdm_out_count(kdm_demod* h, int64_t n_in, int64_t* n_out) {
   if (!h) return fail("null demodulator object");
   if (!n_out) return fail("null n_out pointer");
   if (n_in < 0) return fail("n_in %lld must be >= 0", (long long)n_in);
-  *n_out = ceil_div(h->n_in + n_in, h->D) - ceil_div(h->n_in, h->D);
+  *n_out = stream_outputs(h->n_in, n_in, h->D);
   return 0;
 }
 
@@ -310,14 +257,7 @@ int kdm_process(kdm_demod* h, const void* iq_host, int64_t n_in, void* out_host,
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(h->device));
   const long long bytes = (long long)n_in * 8;
-  if (h->stage_bytes < bytes) {
-    HIP_OK(hipStreamSynchronize(h->stream));
-    if (h->stage) (void)hipFree(h->stage);
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->stage), (size_t)bytes));
-    h->stage_bytes = bytes;
-  }
+  if (int rc = grow_device(&h->stage, &h->stage_bytes, bytes, h->stream)) return rc;
   HIP_OK(hipMemcpyAsync(h->stage, iq_host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
   if (int rc = stream_call(h, h->stage, n_in, h->out, nout)) return rc;
   if (nout > 0) HIP_OK(hipMemcpyAsync(out_host, h->out, (size_t)nout * out_bytes(h), hipMemcpyDeviceToHost, h->stream));
@@ -336,7 +276,7 @@ int kdm_blocks_dev(kdm_demod* h, const void* iq_dev, int64_t block_stride, int64
   if (block_len > h->max_in || nblocks > h->max_in / block_len)
     return fail("%lld blocks of %lld samples exceed max_in %lld", (long long)nblocks, (long long)block_len, h->max_in);
   if (nblocks > 0 && !iq_dev) return fail("null input pointer");
-  if (reinterpret_cast<uintptr_t>(iq_dev) % 8u) return fail("input pointer is not aligned to the 8 bytes of a sample");
+  if (int rc = check_iq_aligned(iq_dev, 8)) return rc;
   const long long M = (block_len - lead - h->T) / h->D + 1;
   if (out_dev && out_stride < M) return fail("out_stride %lld is shorter than the %lld outputs of a block", (long long)out_stride, M);
   if (!out_dev && nblocks * M > h->out_cap)

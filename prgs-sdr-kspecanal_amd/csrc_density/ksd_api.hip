@@ -3,42 +3,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/ksa_density.h"
 #include "ksd_kernels.hpp"
+#include "../csrc_shared/ksa_host.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return 1;
-}
-
-#define HIP_OK(call)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (call);                                                               \
-    if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-// Entry points run on their object's device and hand the caller's current device back on every exit path.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 constexpr int LDS_PLAIN = 64 << 10;       // dynamic LDS a kernel gets without asking
 constexpr int LDS_OPTIN = 128 << 10;      // what a strip may grow to when it would otherwise be narrower than 64 bytes of a row
@@ -154,10 +125,7 @@ int ksd_create(int32_t device, int32_t nbins, int32_t width, int32_t levels, flo
   d->vec_shape = nbins % 4 == 0 && (d->nstrips == 1 || ((long long)S * d->g) % 4 == 0);
   int rc = 0;
   do {
-    if (hipDeviceGetAttribute(&d->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || d->cus < 1) {
-      rc = fail("hipDeviceGetAttribute(MultiprocessorCount) failed on device %d", device);
-      break;
-    }
+    if ((rc = cu_count(device, &d->cus))) break;
     if (d->lds_bytes > LDS_PLAIN) {
       for (int v = 0; v < 4 && !rc; ++v)
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(add_fn(v & 1, v & 2)), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -172,7 +140,7 @@ int ksd_create(int32_t device, int32_t nbins, int32_t width, int32_t levels, flo
     if (e != hipSuccess) { rc = fail("zeroing the counters failed: %s", hipGetErrorString(e)); break; }
   } while (0);
   if (rc) {
-    if (d->counts) (void)hipFree(d->counts);
+    free_device({d->counts});
     delete d;
     return rc;
   }
@@ -186,30 +154,18 @@ void ksd_destroy(ksd_density* d) {
   (void)hipSetDevice(d->device);
   (void)hipStreamSynchronize(d->stream);
   if (d->ev_stream) (void)hipEventDestroy(d->ev_stream);
-  if (d->counts) (void)hipFree(d->counts);
-  if (d->stage) (void)hipFree(d->stage);
+  free_device({d->counts, d->stage});
   delete d;
 }
 
 int ksd_set_stream(ksd_density* d, void* hip_stream) {
   if (!d) return fail("null density object");
-  hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-  if (ns == d->stream) return 0;
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(d->device));
-  if (!d->ev_stream) HIP_OK(hipEventCreateWithFlags(&d->ev_stream, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(d->ev_stream, d->stream));
-  HIP_OK(hipStreamWaitEvent(ns, d->ev_stream, 0));
-  d->stream = ns;
-  return 0;
+  return hand_over_stream(d->device, &d->stream, &d->ev_stream, hip_stream);
 }
 
 int ksd_synchronize(ksd_density* d) {
   if (!d) return fail("null density object");
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(d->device));
-  HIP_OK(hipStreamSynchronize(d->stream));
-  return 0;
+  return synchronize_on(d->device, d->stream);
 }
 
 int ksd_add_rows_dev(ksd_density* d, const float* rows_dev, int64_t row_stride, int64_t nrows) {
@@ -235,14 +191,7 @@ int ksd_add_rows(ksd_density* d, const float* rows_host, int64_t nrows) {
   HIP_OK(hipSetDevice(d->device));
   const long long piece = std::max<long long>(1, STAGE_BYTES / ((long long)d->nbins * 4));
   const long long need = std::min<long long>(piece, nrows) * d->nbins;
-  if (d->stage_floats < need) {
-    HIP_OK(hipStreamSynchronize(d->stream));
-    if (d->stage) (void)hipFree(d->stage);
-    d->stage = nullptr;
-    d->stage_floats = 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&d->stage), (size_t)need * 4));
-    d->stage_floats = need;
-  }
+  if (int rc = grow_device(&d->stage, &d->stage_floats, need, d->stream)) return rc;
   // the pieces queue one behind the other on the object's stream, so one staging buffer serves them all; rows_seen moves
   // with every piece that was enqueued
   for (long long done = 0; done < nrows;) {

@@ -3,46 +3,17 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/ksa_detect.h"
 #include "kse_kernels.hpp"
+#include "../csrc_shared/ksa_host.hpp"
 
 static_assert(sizeof(kse_emission) == sizeof(ksa::detect::Emission), "kse_emission and the kernels' record are one layout");
 static_assert(KSE_MODE_CA == ksa::detect::MODE_CA && KSE_MODE_GO == ksa::detect::MODE_GO && KSE_MODE_SO == ksa::detect::MODE_SO,
               "the modes of the header are the kernels'");
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return 1;
-}
-
-#define HIP_OK(call)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (call);                                                               \
-    if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-// Entry points run on their object's device and hand the caller's current device back on every exit path.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 constexpr long long MAX_LAUNCH_ROWS = 1ll << 20;        // bounds the per-row scratch, made at creation: 12 MiB
 constexpr long long STAGE_BYTES = 64ll << 20;           // kse_detect_rows: rows cross in pieces of at most this size
@@ -169,9 +140,7 @@ int launch_detect(kse_detector* d, const float* rows_dev, long long row_stride, 
 
 void free_all(kse_detector* d) {
   if (d->ev_stream) (void)hipEventDestroy(d->ev_stream);
-  for (void* p : {(void*)d->hits, (void*)d->events, (void*)d->totals, (void*)d->block_sums, (void*)d->cnt, (void*)d->off,
-                  (void*)d->stage})
-    if (p) (void)hipFree(p);
+  free_device({d->hits, d->events, d->totals, d->block_sums, d->cnt, d->off, d->stage});
   delete d;
 }
 
@@ -200,10 +169,7 @@ int kse_create(int32_t device, int32_t nbins, int32_t train, int32_t guard, floa
   d->lds_bytes = ksa::detect::layout_for(nbins).slot * rows_per_wg(d);
   int rc = 0;
   do {
-    if (hipDeviceGetAttribute(&d->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || d->cus < 1) {
-      rc = fail("hipDeviceGetAttribute(MultiprocessorCount) failed on device %d", device);
-      break;
-    }
+    if ((rc = cu_count(device, &d->cus))) break;
     hipError_t e = hipSuccess;
     const int lds_max = ksa::detect::layout_for(KSE_MAX_NBINS).slot;      // one value for every object of the process
     for (int v = 0; v < 4 && e == hipSuccess; ++v)
@@ -242,23 +208,12 @@ void kse_destroy(kse_detector* d) {
 
 int kse_set_stream(kse_detector* d, void* hip_stream) {
   if (!d) return fail("null detector object");
-  hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-  if (ns == d->stream) return 0;
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(d->device));
-  if (!d->ev_stream) HIP_OK(hipEventCreateWithFlags(&d->ev_stream, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(d->ev_stream, d->stream));
-  HIP_OK(hipStreamWaitEvent(ns, d->ev_stream, 0));
-  d->stream = ns;
-  return 0;
+  return hand_over_stream(d->device, &d->stream, &d->ev_stream, hip_stream);
 }
 
 int kse_synchronize(kse_detector* d) {
   if (!d) return fail("null detector object");
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(d->device));
-  HIP_OK(hipStreamSynchronize(d->stream));
-  return 0;
+  return synchronize_on(d->device, d->stream);
 }
 
 int kse_detect_rows_dev(kse_detector* d, const float* rows_dev, int64_t row_stride, int64_t nrows, int32_t* row_count_dev,
@@ -283,14 +238,7 @@ int kse_detect_rows(kse_detector* d, const float* rows_host, int64_t nrows) {
   HIP_OK(hipSetDevice(d->device));
   const long long piece = std::min(MAX_LAUNCH_ROWS, std::max<long long>(1, STAGE_BYTES / ((long long)d->nbins * 4)));
   const long long need = std::min<long long>(piece, nrows) * d->nbins;
-  if (d->stage_floats < need) {
-    HIP_OK(hipStreamSynchronize(d->stream));
-    if (d->stage) (void)hipFree(d->stage);
-    d->stage = nullptr;
-    d->stage_floats = 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&d->stage), (size_t)need * 4));
-    d->stage_floats = need;
-  }
+  if (int rc = grow_device(&d->stage, &d->stage_floats, need, d->stream)) return rc;
   // the pieces queue one behind the other on the object's stream, so one staging buffer serves them all
   for (long long done = 0; done < nrows;) {
     const long long n = std::min(piece, nrows - done);

@@ -3,46 +3,17 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <limits>
-#include <string>
 #include <vector>
 
 #include "../../include/ksa_mask.h"
 #include "ksm_kernels.hpp"
+#include "../csrc_shared/ksa_host.hpp"
 
 static_assert(sizeof(ksm_event) == sizeof(ksa::mask::Event), "ksm_event and the kernels' record are one layout");
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return 1;
-}
-
-#define HIP_OK(call)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (call);                                                               \
-    if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-// Entry points run on their object's device and hand the caller's current device back on every exit path.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 constexpr int MAX_CHUNK_ROWS = 1 << 16;         // a lane's uint32 hit counters cannot wrap
 constexpr int MIN_CHUNK_ROWS = 8;               // below this a workgroup's line loads and flush outweigh its rows
@@ -109,23 +80,12 @@ void plan_chunks(const ksm_mask* m, int nstrips, long long n, int* chunk_rows, i
   *nchunks = (int)((n + rows - 1) / rows);
 }
 
-int need_scratch(ksm_mask* m, long long rows) {
-  if (m->rec_rows >= rows) return 0;
-  HIP_OK(hipStreamSynchronize(m->stream));
-  if (m->rec) (void)hipFree(m->rec);
-  m->rec = nullptr;
-  m->rec_rows = 0;
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(&m->rec), (size_t)rows * sizeof(ksa::mask::RowRec)));
-  m->rec_rows = rows;
-  return 0;
-}
-
 // rows [0, nrows) of rows_dev, numbered from m->rows_seen; rows_seen moves with every launch that was enqueued
 int launch_check(ksm_mask* m, const float* rows_dev, long long row_stride, long long nrows, uint8_t* row_event_dev) {
   using namespace ksa::mask;
   const bool vec = vec_for(m, rows_dev, row_stride);
   const int nstrips = strips_of(m, vec);
-  if (int rc = need_scratch(m, std::min(nrows, MAX_LAUNCH_ROWS))) return rc;
+  if (int rc = grow_device(&m->rec, &m->rec_rows, std::min(nrows, MAX_LAUNCH_ROWS), m->stream)) return rc;
   for (long long done = 0; done < nrows;) {
     const long long n = std::min(nrows - done, MAX_LAUNCH_ROWS);
     HIP_OK(hipMemsetAsync(m->rec, 0, (size_t)n * sizeof(RowRec), m->stream));
@@ -170,9 +130,7 @@ int launch_check(ksm_mask* m, const float* rows_dev, long long row_stride, long 
 
 void free_all(ksm_mask* m) {
   if (m->ev_stream) (void)hipEventDestroy(m->ev_stream);
-  for (void* p : {(void*)m->upper, (void*)m->lower, (void*)m->hits, (void*)m->events, (void*)m->totals, (void*)m->block_counts,
-                  (void*)m->rec, (void*)m->stage})
-    if (p) (void)hipFree(p);
+  free_device({m->upper, m->lower, m->hits, m->events, m->totals, m->block_counts, m->rec, m->stage});
   delete m;
 }
 
@@ -201,10 +159,7 @@ int ksm_create(int32_t device, int32_t nbins, const float* upper_host, const flo
   m->no_lower.assign((size_t)nbins, -std::numeric_limits<float>::infinity());
   int rc = 0;
   do {
-    if (hipDeviceGetAttribute(&m->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || m->cus < 1) {
-      rc = fail("hipDeviceGetAttribute(MultiprocessorCount) failed on device %d", device);
-      break;
-    }
+    if ((rc = cu_count(device, &m->cus))) break;
     const size_t line = (size_t)nbins * 4, events = (size_t)capacity * sizeof(ksa::mask::Event);
     const size_t counts = (size_t)(MAX_LAUNCH_ROWS / ksa::mask::SCAN_THREADS) * sizeof(int);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->upper), line);
@@ -238,23 +193,12 @@ void ksm_destroy(ksm_mask* m) {
 
 int ksm_set_stream(ksm_mask* m, void* hip_stream) {
   if (!m) return fail("null mask object");
-  hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-  if (ns == m->stream) return 0;
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(m->device));
-  if (!m->ev_stream) HIP_OK(hipEventCreateWithFlags(&m->ev_stream, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(m->ev_stream, m->stream));
-  HIP_OK(hipStreamWaitEvent(ns, m->ev_stream, 0));
-  m->stream = ns;
-  return 0;
+  return hand_over_stream(m->device, &m->stream, &m->ev_stream, hip_stream);
 }
 
 int ksm_synchronize(ksm_mask* m) {
   if (!m) return fail("null mask object");
-  DeviceGuard dev_guard;
-  HIP_OK(hipSetDevice(m->device));
-  HIP_OK(hipStreamSynchronize(m->stream));
-  return 0;
+  return synchronize_on(m->device, m->stream);
 }
 
 int ksm_check_rows_dev(ksm_mask* m, const float* rows_dev, int64_t row_stride, int64_t nrows, uint8_t* row_event_dev) {
@@ -278,14 +222,7 @@ int ksm_check_rows(ksm_mask* m, const float* rows_host, int64_t nrows) {
   HIP_OK(hipSetDevice(m->device));
   const long long piece = std::min(MAX_LAUNCH_ROWS, std::max<long long>(1, STAGE_BYTES / ((long long)m->nbins * 4)));
   const long long need = std::min<long long>(piece, nrows) * m->nbins;
-  if (m->stage_floats < need) {
-    HIP_OK(hipStreamSynchronize(m->stream));
-    if (m->stage) (void)hipFree(m->stage);
-    m->stage = nullptr;
-    m->stage_floats = 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&m->stage), (size_t)need * 4));
-    m->stage_floats = need;
-  }
+  if (int rc = grow_device(&m->stage, &m->stage_floats, need, m->stream)) return rc;
   // the pieces queue one behind the other on the object's stream, so one staging buffer serves them all
   for (long long done = 0; done < nrows;) {
     const long long n = std::min(piece, nrows - done);

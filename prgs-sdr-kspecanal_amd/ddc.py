@@ -3,17 +3,14 @@ libksa.so) and the DownConverter class over it.  The frequency of interest is sh
 by D; the complex64 result in device memory is what the engine's frames_dev / curscan_dev / scan entry points already accept,
 and the same fftSize then resolves D times finer bins.  There is no fallback: a missing library raises."""
 import ctypes as C
-import os
 from fractions import Fraction
 
 import numpy as np
 
-from . import _lib
+from ._companion import Binding, Companion
 from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
-from .engine import _ptr, window_table
+from .engine import DevArray, _ptr, window_table
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libksa_ddc.so")
 ABI_VERSION = 1
 MAX_DECIM, MAX_TAPS, MAX_IN = 1024, 16384, 2 ** 28 - 1
 FORM_TILE, FORM_REDUCE = 0, 1
@@ -42,37 +39,9 @@ SIGNATURES = {
 }
 
 
-def load(path=LIB_PATH):
-    _lib._preload_torch_hip_runtime()      # every library binds the one HIP runtime torch mapped
-    if not os.path.exists(path):
-        raise KsaError("libksa_ddc.so is missing at %s -- build it with `python __graft_entry__.py` "
-                       "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
-    lib = C.CDLL(path)
-    lib.kdc_abi_version.restype = C.c_int
-    if lib.kdc_abi_version() != ABI_VERSION:
-        raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
-                       % (path, lib.kdc_abi_version(), ABI_VERSION))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-_loaded = None
-
-
-def lib():
-    """libksa_ddc.so, loaded on first use (the spectrum engine alone does not need it)."""
-    global _loaded
-    if _loaded is None:
-        _loaded = load()
-    return _loaded
-
-
-def check(rc):
-    if rc != 0:
-        raise KsaError(lib().kdc_last_error().decode("utf-8", "replace"))
+_bind = Binding("libksa_ddc.so", "kdc_", ABI_VERSION, SIGNATURES)
+LIB_PATH = _bind.path
+load, lib, check = _bind.load, _bind.lib, _bind.check
 
 
 def phase_inc_for(freq, sampling_rate):
@@ -94,24 +63,15 @@ def ddc_lowpass(decim, taps_per_phase=8, cutoff=0.8, window="hamming"):
     return (h / h.sum()).astype(np.float32)
 
 
-class DevArray:
-    """View of library-owned device memory for torch.as_tensor (via __cuda_array_interface__), complex64."""
-
-    def __init__(self, ptr, shape, owner):
-        self._owner = owner
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<c8", "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
-
-
-class DownConverter:
+class DownConverter(Companion):
     """Mixer, real FIR low-pass and decimator by `decim` for one IQ stream on one GPU; the contract is include/ksa_ddc.h.
     The tuning is either phase_inc (2^64 = one turn per input sample) or freq with sampling_rate."""
+    _binding, _info_fields = _bind, ("threads", "lds_bytes", "vgprs", "grid", "tile_out", "form")
 
     def __init__(self, fmt, decim, taps, freq=0.0, sampling_rate=1.0, phase_inc=None, max_in=1 << 20, device=0, stream=None,
                  u8_offset=127.5, u8_scale=127.5):
         self.fmt, self.decim, self.device, self.max_in = int(fmt), int(decim), int(device), int(max_in)
         self.sampling_rate = sampling_rate
-        self._h = None
         self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         self.ntaps = int(self.taps.size)
         inc = phase_inc_for(freq, sampling_rate) if phase_inc is None else int(phase_inc) % 2 ** 64
@@ -125,30 +85,6 @@ class DownConverter:
         self._out, self.out_capacity = p.value, cap.value
         if stream is not None:
             self.set_stream(stream)
-
-    # -- lifetime ---------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().kdc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream):
-        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
-        check(lib().kdc_set_stream(self._h, C.c_void_p(stream or 0)))
-
-    def synchronize(self):
-        check(lib().kdc_synchronize(self._h))
-
-    def kernel_info(self):
-        v = [C.c_int32() for _ in range(6)]
-        check(lib().kdc_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("threads", "lds_bytes", "vgprs", "grid", "tile_out", "form"), [x.value for x in v]))
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):
@@ -222,7 +158,7 @@ class DownConverter:
     @property
     def out(self):
         """The object's output buffer, complex64 [out_capacity], for torch.as_tensor."""
-        return DevArray(self._out, (self.out_capacity,), self)
+        return DevArray(self._out, (self.out_capacity,), self, "<c8")
 
     @property
     def out_ptr(self):

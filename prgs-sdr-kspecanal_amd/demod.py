@@ -3,18 +3,15 @@ libksa.so) and the Demodulator class over it.  The complex64 block that the down
 complex64 capture) becomes amplitude, frequency or phase versus time, low-pass filtered and decimated by D, as float32 or as
 int16 PCM.  There is no fallback: a missing library raises."""
 import ctypes as C
-import os
 import wave
 
 import numpy as np
 
-from . import _lib
+from ._companion import Binding, Companion
 from ._lib import KsaError
-from .engine import _ptr
+from .engine import DevArray, _ptr
 from .ddc import ddc_lowpass
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libksa_demod.so")
 ABI_VERSION = 1
 MODE_AM, MODE_FM, MODE_PM = 0, 1, 2
 MODES = {"am": MODE_AM, "fm": MODE_FM, "pm": MODE_PM}
@@ -46,37 +43,9 @@ SIGNATURES = {
 }
 
 
-def load(path=LIB_PATH):
-    _lib._preload_torch_hip_runtime()      # every library binds the one HIP runtime torch mapped
-    if not os.path.exists(path):
-        raise KsaError("libksa_demod.so is missing at %s -- build it with `python __graft_entry__.py` "
-                       "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
-    lib = C.CDLL(path)
-    lib.kdm_abi_version.restype = C.c_int
-    if lib.kdm_abi_version() != ABI_VERSION:
-        raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
-                       % (path, lib.kdm_abi_version(), ABI_VERSION))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-_loaded = None
-
-
-def lib():
-    """libksa_demod.so, loaded on first use (the spectrum engine alone does not need it)."""
-    global _loaded
-    if _loaded is None:
-        _loaded = load()
-    return _loaded
-
-
-def check(rc):
-    if rc != 0:
-        raise KsaError(lib().kdm_last_error().decode("utf-8", "replace"))
+_bind = Binding("libksa_demod.so", "kdm_", ABI_VERSION, SIGNATURES)
+LIB_PATH = _bind.path
+load, lib, check = _bind.load, _bind.lib, _bind.check
 
 
 def demod_taps(decim, taps_per_phase=8, cutoff=0.8, window="hamming", gain=1.0, deemph_us=None, sampling_rate=None,
@@ -114,21 +83,12 @@ def write_wav(path, pcm_int16, rate):
         w.writeframes(pcm.reshape(-1).astype("<i2").tobytes())
 
 
-class DevArray:
-    """View of library-owned device memory for torch.as_tensor (via __cuda_array_interface__), float32 or int16."""
-
-    def __init__(self, ptr, shape, typestr, owner):
-        self._owner = owner
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
-
-
-class Demodulator:
+class Demodulator(Companion):
     """Detector (mode "am" | "fm" | "pm"), real FIR low-pass and decimator by `decim` for one complex64 IQ stream on one GPU;
     the contract is include/ksa_demod.h.  out_fmt "f32" gives float32 outputs, "s16" int16 PCM of y * pcm_scale."""
+    _binding, _info_fields = _bind, ("threads", "lds_bytes", "vgprs", "grid", "tile_out")
 
     def __init__(self, mode, decim, taps, out_fmt="f32", pcm_scale=32767.0, max_in=1 << 20, device=0, stream=None):
-        self._h = None
         if isinstance(mode, str) and mode.lower() not in MODES:
             raise KsaError("unknown mode [%s], expected one of %s" % (mode, "|".join(MODES)))
         if isinstance(out_fmt, str) and out_fmt.lower() not in OUT_FMTS:
@@ -149,30 +109,6 @@ class Demodulator:
         self._out, self.out_capacity = p.value, cap.value
         if stream is not None:
             self.set_stream(stream)
-
-    # -- lifetime ---------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().kdm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream):
-        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
-        check(lib().kdm_set_stream(self._h, C.c_void_p(stream or 0)))
-
-    def synchronize(self):
-        check(lib().kdm_synchronize(self._h))
-
-    def kernel_info(self):
-        v = [C.c_int32() for _ in range(5)]
-        check(lib().kdm_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("threads", "lds_bytes", "vgprs", "grid", "tile_out"), [x.value for x in v]))
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):
@@ -235,4 +171,4 @@ class Demodulator:
     @property
     def out(self):
         """The object's output buffer, float32 or int16 [out_capacity], for torch.as_tensor."""
-        return DevArray(self._out, (self.out_capacity,), "<i2" if self.out_fmt == OUT_S16 else "<f4", self)
+        return DevArray(self._out, (self.out_capacity,), self, "<i2" if self.out_fmt == OUT_S16 else "<f4")

@@ -3,16 +3,13 @@ companion of libksa.so) and the SpectrumDensity class over it.  A bitmap of leve
 many spectra passed through that level at that frequency; it consumes the per-frame dB rows the engine already writes to
 device memory (frames_dev(cur_db=...), curscan_dev(out_mode=OUT_DB)).  There is no fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _lib
+from ._companion import Binding, Companion
 from ._lib import KsaError
-from .engine import _ptr
+from .engine import DevArray, _ptr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libksa_density.so")
 ABI_VERSION = 1
 
 _P = C.c_void_p
@@ -37,52 +34,16 @@ SIGNATURES = {
 }
 
 
-def load(path=LIB_PATH):
-    _lib._preload_torch_hip_runtime()      # both libraries bind the one HIP runtime torch mapped
-    if not os.path.exists(path):
-        raise KsaError("libksa_density.so is missing at %s -- build it with `python __graft_entry__.py` "
-                       "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
-    lib = C.CDLL(path)
-    lib.ksd_abi_version.restype = C.c_int
-    if lib.ksd_abi_version() != ABI_VERSION:
-        raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
-                       % (path, lib.ksd_abi_version(), ABI_VERSION))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
+_bind = Binding("libksa_density.so", "ksd_", ABI_VERSION, SIGNATURES)
+LIB_PATH = _bind.path
+load, lib, check = _bind.load, _bind.lib, _bind.check
 
 
-_loaded = None
-
-
-def lib():
-    """libksa_density.so, loaded on first use (the spectrum engine alone does not need it)."""
-    global _loaded
-    if _loaded is None:
-        _loaded = load()
-    return _loaded
-
-
-def check(rc):
-    if rc != 0:
-        raise KsaError(lib().ksd_last_error().decode("utf-8", "replace"))
-
-
-class _CountsView:
-    """View of the library-owned counters for torch.as_tensor (via __cuda_array_interface__)."""
-
-    def __init__(self, ptr, shape, owner):
-        self._owner = owner
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i8", "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
-
-
-class SpectrumDensity:
+class SpectrumDensity(Companion):
     """int64 counts[levels + 1][width] on one GPU: row k < levels counts the dB values in [lo + k*step, lo + (k+1)*step) (the
     first and last level also take what lies below and above the range), the extra last row counts NaNs; width must divide
     nbins and nbins / width adjacent bins share a column.  The float32 rule is stated in include/ksa_density.h."""
+    _binding, _info_fields = _bind, ("threads", "lds_bytes", "vgprs", "grid", "strip_cols", "lds_optin")
 
     def __init__(self, nbins, width=None, levels=256, lo_db=-140.0, hi_db=0.0, device=0, stream=None):
         self.nbins = int(nbins)
@@ -90,36 +51,11 @@ class SpectrumDensity:
         self.levels = int(levels)
         self.lo_db, self.hi_db = float(lo_db), float(hi_db)
         self.device = int(device)
-        self._h = None
         h = C.c_void_p()
         check(lib().ksd_create(self.device, self.nbins, self.width, self.levels, self.lo_db, self.hi_db, C.byref(h)))
         self._h = h
         if stream is not None:
             self.set_stream(stream)
-
-    # -- lifetime ---------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().ksd_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream):
-        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
-        check(lib().ksd_set_stream(self._h, C.c_void_p(stream or 0)))
-
-    def synchronize(self):
-        check(lib().ksd_synchronize(self._h))
-
-    def kernel_info(self):
-        v = [C.c_int32() for _ in range(6)]
-        check(lib().ksd_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("threads", "lds_bytes", "vgprs", "grid", "strip_cols", "lds_optin"), [x.value for x in v]))
 
     # -- counting ---------------------------------------------------------------------------------
     def add_rows_dev(self, rows, nrows, row_stride=None):
@@ -165,7 +101,7 @@ class SpectrumDensity:
     def counts_dev(self):
         p = C.c_void_p()
         check(lib().ksd_counts_dev(self._h, C.byref(p)))
-        return _CountsView(p.value, (self.levels + 1, self.width), self)
+        return DevArray(p.value, (self.levels + 1, self.width), self, "<i8")
 
     # -- host helpers -----------------------------------------------------------------------------
     def level_edges(self):

@@ -5,16 +5,13 @@ bin, stop bin, peak, floor) and every bin counts the rows in which it lay inside
 rows the engine already writes to device memory (frames_dev(cur_db=...), curscan_dev(out_mode=OUT_DB)).  There is no fallback:
 a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _lib
+from ._companion import Binding, Companion
 from ._lib import KsaError
-from .engine import _ptr
+from .engine import DevArray, _ptr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libksa_detect.so")
 ABI_VERSION = 1
 MIN_NBINS, MAX_NBINS = 16, 16384
 MAX_TRAIN, MAX_GUARD, MAX_GAP = 1024, 256, 1024
@@ -52,37 +49,9 @@ SIGNATURES = {
 }
 
 
-def load(path=LIB_PATH):
-    _lib._preload_torch_hip_runtime()      # every library binds the one HIP runtime torch mapped
-    if not os.path.exists(path):
-        raise KsaError("libksa_detect.so is missing at %s -- build it with `python __graft_entry__.py` "
-                       "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
-    lib = C.CDLL(path)
-    lib.kse_abi_version.restype = C.c_int
-    if lib.kse_abi_version() != ABI_VERSION:
-        raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
-                       % (path, lib.kse_abi_version(), ABI_VERSION))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-_loaded = None
-
-
-def lib():
-    """libksa_detect.so, loaded on first use (the spectrum engine alone does not need it)."""
-    global _loaded
-    if _loaded is None:
-        _loaded = load()
-    return _loaded
-
-
-def check(rc):
-    if rc != 0:
-        raise KsaError(lib().kse_last_error().decode("utf-8", "replace"))
+_bind = Binding("libksa_detect.so", "kse_", ABI_VERSION, SIGNATURES)
+LIB_PATH = _bind.path
+load, lib, check = _bind.load, _bind.lib, _bind.check
 
 
 def _mode(mode):
@@ -102,25 +71,16 @@ def emission_freqs(ev, freqs):
     return (lo + hi) / 2, (ev["bin_hi"] - ev["bin_lo"] + 1) * step
 
 
-class _HitsView:
-    """View of the library-owned hit counters for torch.as_tensor (via __cuda_array_interface__)."""
-
-    def __init__(self, ptr, shape, owner):
-        self._owner = owner
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i8", "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
-
-
-class SignalDetector:
+class SignalDetector(Companion):
     """A CFAR detector over rows of nbins bins on one GPU: `train` training and `guard` guard cells on either side, a
     threshold in dB above the estimated floor, mode ca | go | so; detected runs shorter than min_width are dropped, gaps of at
     most max_gap bins are bridged.  It holds int64 hits[nbins] and the first `capacity` emission records in ascending
     (row, bin_lo) order.  The integer rule is stated in include/ksa_detect.h."""
+    _binding, _info_fields = _bind, ("threads", "lds_bytes", "vgprs", "grid", "vec", "rows_per_wg")
 
     def __init__(self, nbins, train, guard, threshold_db, mode="ca", min_width=1, max_gap=0, capacity=4096, device=0,
                  stream=None):
         self.nbins, self.capacity, self.device = int(nbins), int(capacity), int(device)
-        self._h = None
         self.params = (int(train), int(guard), float(threshold_db), _mode(mode), int(min_width), int(max_gap))
         h = C.c_void_p()
         t, g, thr, m, w, k = self.params
@@ -128,30 +88,6 @@ class SignalDetector:
         self._h = h
         if stream is not None:
             self.set_stream(stream)
-
-    # -- lifetime ---------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().kse_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream):
-        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
-        check(lib().kse_set_stream(self._h, C.c_void_p(stream or 0)))
-
-    def synchronize(self):
-        check(lib().kse_synchronize(self._h))
-
-    def kernel_info(self):
-        v = [C.c_int32() for _ in range(6)]
-        check(lib().kse_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("threads", "lds_bytes", "vgprs", "grid", "vec", "rows_per_wg"), [x.value for x in v]))
 
     # -- detection --------------------------------------------------------------------------------
     def detect_rows_dev(self, rows, nrows=None, row_stride=None, row_count=None, floor=None):
@@ -235,4 +171,4 @@ class SignalDetector:
     def hits_view(self):
         p = C.c_void_p()
         check(lib().kse_hits_dev(self._h, C.byref(p)))
-        return _HitsView(p.value, (self.nbins,), self)
+        return DevArray(p.value, (self.nbins,), self, "<i8")

@@ -138,11 +138,12 @@ def _fixed_fmt(a):
 
 
 class DevArray:
-    """View of library-owned device memory for torch.as_tensor (via __cuda_array_interface__)."""
+    """View of library-owned device memory for torch.as_tensor (via __cuda_array_interface__); typestr names the element type
+    ("<f4" float32, "<c8" complex64, "<i8" int64, "<i2" int16)."""
 
-    def __init__(self, ptr, shape, owner):
+    def __init__(self, ptr, shape, owner, typestr="<f4"):
         self._owner = owner
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False),
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
                                          "version": 2, "strides": None}
 
 

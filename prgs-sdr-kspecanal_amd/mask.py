@@ -4,16 +4,13 @@ line; the frames that cross a line are reported (which, where, by how much) and 
 consumes the per-frame dB rows the engine already writes to device memory (frames_dev(cur_db=...),
 curscan_dev(out_mode=OUT_DB)).  There is no fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _lib
+from ._companion import Binding, Companion
 from ._lib import KsaError
-from .engine import _ptr
+from .engine import DevArray, _ptr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libksa_mask.so")
 ABI_VERSION = 1
 MAX_CAPACITY = 1 << 20
 
@@ -48,37 +45,9 @@ SIGNATURES = {
 }
 
 
-def load(path=LIB_PATH):
-    _lib._preload_torch_hip_runtime()      # every library binds the one HIP runtime torch mapped
-    if not os.path.exists(path):
-        raise KsaError("libksa_mask.so is missing at %s -- build it with `python __graft_entry__.py` "
-                       "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
-    lib = C.CDLL(path)
-    lib.ksm_abi_version.restype = C.c_int
-    if lib.ksm_abi_version() != ABI_VERSION:
-        raise KsaError("%s has ABI %d, this binding expects %d -- rebuild it (python __graft_entry__.py)"
-                       % (path, lib.ksm_abi_version(), ABI_VERSION))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-_loaded = None
-
-
-def lib():
-    """libksa_mask.so, loaded on first use (the spectrum engine alone does not need it)."""
-    global _loaded
-    if _loaded is None:
-        _loaded = load()
-    return _loaded
-
-
-def check(rc):
-    if rc != 0:
-        raise KsaError(lib().ksm_last_error().decode("utf-8", "replace"))
+_bind = Binding("libksa_mask.so", "ksm_", ABI_VERSION, SIGNATURES)
+LIB_PATH = _bind.path
+load, lib, check = _bind.load, _bind.lib, _bind.check
 
 
 def learn_mask(rows, margin_db):
@@ -92,15 +61,6 @@ def learn_mask(rows, margin_db):
     return up
 
 
-class _HitsView:
-    """View of the library-owned hit counters for torch.as_tensor (via __cuda_array_interface__)."""
-
-    def __init__(self, ptr, shape, owner):
-        self._owner = owner
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i8", "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
-
-
 def _line(values, nbins, name):
     a = np.ascontiguousarray(values, dtype=np.float32)
     if a.ndim == 0:
@@ -110,15 +70,15 @@ def _line(values, nbins, name):
     return a
 
 
-class SpectrumMask:
+class SpectrumMask(Companion):
     """An upper and a lower limit line over nbins bins on one GPU, int64 hits[3][nbins] (over, under, NaN) and the first
     `capacity` event records in ascending row order.  A row is an event when at least min_bins of its bins crossed a line or
     any is NaN.  The float32 rule is stated in include/ksa_mask.h."""
+    _binding, _info_fields = _bind, ("threads", "lds_bytes", "vgprs", "grid", "vec")
 
     def __init__(self, nbins, upper, lower=None, min_bins=1, capacity=4096, device=0, stream=None):
         self.nbins = int(nbins)
         self.min_bins, self.capacity, self.device = int(min_bins), int(capacity), int(device)
-        self._h = None
         self.upper = _line(upper, self.nbins, "upper")
         self.lower = None if lower is None else _line(lower, self.nbins, "lower")
         h = C.c_void_p()
@@ -127,30 +87,6 @@ class SpectrumMask:
         self._h = h
         if stream is not None:
             self.set_stream(stream)
-
-    # -- lifetime ---------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().ksm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream):
-        """stream: a hipStream_t as int (torch.cuda.current_stream().cuda_stream) or None."""
-        check(lib().ksm_set_stream(self._h, C.c_void_p(stream or 0)))
-
-    def synchronize(self):
-        check(lib().ksm_synchronize(self._h))
-
-    def kernel_info(self):
-        v = [C.c_int32() for _ in range(5)]
-        check(lib().ksm_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("threads", "lds_bytes", "vgprs", "grid", "vec"), [x.value for x in v]))
 
     # -- checking ---------------------------------------------------------------------------------
     def check_rows_dev(self, rows, nrows=None, row_stride=None, row_event=None):
@@ -227,4 +163,4 @@ class SpectrumMask:
     def hits_view(self):
         p = C.c_void_p()
         check(lib().ksm_hits_dev(self._h, C.byref(p)))
-        return _HitsView(p.value, (3, self.nbins), self)
+        return DevArray(p.value, (3, self.nbins), self, "<i8")
