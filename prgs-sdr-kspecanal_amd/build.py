@@ -1,6 +1,6 @@
-"""Build the eight shared libraries for gfx950 with hipcc, one translation unit each (PRODUCTS below).  In-tree, no JIT cache:
-every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's sources with
--DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
+"""Build the shared libraries for gfx950 with hipcc, one translation unit each (PRODUCTS and MORE_PRODUCTS below).  In-tree, no
+JIT cache: every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's
+sources with -DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
 import os
 import shutil
 import subprocess
@@ -21,6 +21,10 @@ PRODUCTS = {
     "libksa_demod.so": ("csrc_demod", "kdm_api.hip", "ksa_demod.h", []),
     "libksa_chan.so": ("csrc_chan", "kch_api.hip", "ksa_chan.h", []),
 }
+# the companions that came after those eight, in a table of the same shape: same FLAGS, same dependency on csrc_shared/
+MORE_PRODUCTS = {
+    "libksa_resamp.so": ("csrc_resamp", "krs_api.hip", "ksa_resamp.h", []),
+}
 OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 
@@ -33,7 +37,7 @@ def _files(subdir):
 def _sources(product):
     """Every file the product depends on: its directory, its header and, for a companion library, csrc_shared/ (which csrc/
     does not include)."""
-    subdir, _, header, _ = PRODUCTS[product]
+    subdir, _, header, _ = PRODUCTS[product] if product in PRODUCTS else MORE_PRODUCTS[product]
     shared = _files("csrc_shared") if subdir != "csrc" else []
     return _files(subdir) + shared + [os.path.join(HERE, "..", "include", header)]
 
@@ -45,20 +49,22 @@ def sources():
 # product's path -> (the .hip that is compiled, extra flags, every file the product depends on)
 JOBS = {os.path.join(HERE, name): (os.path.join(HERE, subdir, hip), extra, lambda name=name: _sources(name))
         for name, (subdir, hip, _, extra) in PRODUCTS.items()}
+MORE_JOBS = {os.path.join(HERE, name): (os.path.join(HERE, subdir, hip), extra, lambda name=name: _sources(name))
+             for name, (subdir, hip, _, extra) in MORE_PRODUCTS.items()}
 
 
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(s) > t for s in JOBS[out][2]())
+    return any(os.path.getmtime(s) > t for s in (JOBS[out] if out in JOBS else MORE_JOBS[out])[2]())
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the eight libraries side by side).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the libraries side by side, JOBS then MORE_JOBS).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, (src, extra, _) in JOBS.items():
+    for out, (src, extra, _) in list(JOBS.items()) + list(MORE_JOBS.items()):
         if not force and not is_stale(out):
             continue
         cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]

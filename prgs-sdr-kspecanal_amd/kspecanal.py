@@ -38,7 +38,10 @@ audio at samplingRate / (zoom D x audioDecim), rounded to an integer), `channels
 instead of `zoom`: a polyphase channelizer in front of the engine -- every frame's capture becomes all M channels of the band at
 once, each at samplingRate x O / M, channel `pick` goes on to the engine (and to `demod`, which it satisfies in place of
 `zoom`), and the mean power of every channel over the run is handed off as d['channelsPower'] in dB with d['channelsFreqs'];
-default empty = off) and `channelsSave` (an .npz of power_db, freqs and the parameters).
+default empty = off), `channelsSave` (an .npz of power_db, freqs and the parameters) and `audioRate` (HZ[:tapsPerPhase],
+zeroSpan only, needs `demod`: the demodulator then leaves float32 audio on the GPU and a polyphase L / M resampler, L / M = HZ
+over the demodulator's rate, reduced, turns every block of it into int16 PCM at exactly HZ, which is what d['demodRate'] and the
+WAV header then say; default empty = off).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -69,6 +72,8 @@ from . import demod as _demod
 from .demod import Demodulator, demod_taps, write_wav
 from . import chan as _chan
 from .chan import Channelizer, chan_prototype, channel_freqs
+from . import resamp as _resamp
+from .resamp import Resampler, resample_taps, rate_ratio
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -101,7 +106,7 @@ _KEYS = {
     "DENSITY": ("density", str), "DENSITYSAVE": ("densitySave", str), "MASK": ("mask", str), "MASKSAVE": ("maskSave", str),
     "ZOOM": ("zoom", str), "DETECT": ("detect", str), "DETECTSAVE": ("detectSave", str),
     "DEMOD": ("demod", str), "DEMODSAVE": ("demodSave", str),
-    "CHANNELS": ("channels", str), "CHANNELSSAVE": ("channelsSave", str),
+    "CHANNELS": ("channels", str), "CHANNELSSAVE": ("channelsSave", str), "AUDIORATE": ("audioRate", str),
 }
 
 
@@ -119,6 +124,7 @@ def defaults():
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
         "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
+        "audioRate": "",
     }
 
 
@@ -205,6 +211,7 @@ def handle_args(d, argv=None):
     _handle_channels(d)
     _handle_detect(d)
     _handle_demod(d)
+    _handle_resample(d)
     return d
 
 
@@ -504,6 +511,50 @@ def _handle_demod(d):
                            out_per_block=(d["fullSize"] - lead - ntaps) // decim + 1, rate=rate)
 
 
+RESAMPLE_RULE = ("audioRate wants HZ[:tapsPerPhase] with a whole HZ >= 1 and an integer tapsPerPhase >= 1 (default 8); it needs demod, "
+                 "a whole audio rate samplingRate / (zoom D x audioDecim) in front of it, L / M = HZ over that rate, reduced, with "
+                 "L <= %d, M <= %d and M <= %d L, at most %d taps per phase and %d taps in all, and a block long enough for one "
+                 "output" % (_resamp.MAX_L, _resamp.MAX_M, _resamp.MAX_RATIO, _resamp.MAX_PHASE_TAPS, _resamp.MAX_TAPS))
+
+
+def _handle_resample(d):
+    """audioRate HZ[:tapsPerPhase] (additive, zeroSpan only, behind demod): d['resample.spec'] = dict(rate, rate_in, L, M,
+    taps_per_phase, phase_taps, in_per_block, out_per_block), or None when the key is off."""
+    d["resample.spec"] = None
+    text = d["audioRate"]
+    if not text:
+        return
+    try:
+        parts = text.split(":")
+        if not 1 <= len(parts) <= 2:
+            raise ValueError(text)
+        hz = float(parts[0])
+        tpp = int(parts[1]) if len(parts) > 1 else 8
+        if not (np.isfinite(hz) and hz >= 1 and hz == int(hz) and tpp >= 1):
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: audioRate [{}]: {}".format(text, RESAMPLE_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: audioRate [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: audioRate [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    dspec = d["demod.spec"]
+    if dspec is None:
+        prg_quit(d, "ERROR:handle_args: audioRate [{}] needs demod: {}".format(text, RESAMPLE_RULE))
+    front = d["zoom.spec"] if d["zoom.spec"] is not None else d["chan.spec"]
+    try:
+        L, M = rate_ratio(d["samplingRate"] / (front["decim"] * dspec["decim"]), hz)
+        P = len(resample_taps(L, M, tpp)) // L
+    except KsaError as e:
+        prg_quit(d, "ERROR:handle_args: audioRate [{}]: {}: {}".format(text, e, RESAMPLE_RULE))
+    per_block = -(-dspec["out_per_block"] * L // M) - -(-(P - 1) * L // M)
+    if per_block < 1:
+        prg_quit(d, "ERROR:handle_args: audioRate [{}]: {}".format(text, RESAMPLE_RULE))
+    d["resample.spec"] = dict(rate=int(hz), rate_in=dspec["rate"], L=L, M=M, taps_per_phase=tpp, phase_taps=P,
+                              in_per_block=dspec["out_per_block"], out_per_block=per_block)
+
+
 def _handle_pfb(d):
     """pfbTaps P (additive): the polyphase front end.  fullSize becomes P*fftSize (P segments of fftSize samples per
     spectrum), `window` names the taper of the prototype; the within-block overlap and fold have nothing left to do.
@@ -569,6 +620,10 @@ def print_info(d):
         print("INFO: demod [{}]: audio decimation [{}], low-pass of [{}] taps, de-emphasis [{}] us, [{}] samples per block at [{}] Hz; "
               "each block is demodulated on its own and the blocks abut".format(
                   m["mode"], m["decim"], m["ntaps"], m["deemph_us"], m["out_per_block"], m["rate"]))
+    if d.get("resample.spec"):
+        r = d["resample.spec"]
+        print("INFO: audioRate [{}]: [{}] Hz -> [{}] Hz by L / M = [{}] / [{}], [{}] taps per phase, [{}] samples per block".format(
+            r["rate"], r["rate_in"], r["rate"], r["L"], r["M"], r["phase_taps"], r["out_per_block"]))
 
 
 # ------------------------------------------------------------------------------------------ SDR seam
@@ -1171,27 +1226,40 @@ class _DemodFeed:
         fs = d["samplingRate"] / zoom["decim"]
         taps = demod_taps(spec["decim"], spec["taps_per_phase"], deemph_us=spec["deemph_us"],
                           sampling_rate=fs if spec["deemph_us"] is not None else None, dc_block=spec["mode"] == "am")
-        self.dem = Demodulator(spec["mode"], spec["decim"], taps, out_fmt="s16", pcm_scale=DEMOD_PCM_SCALE,
-                               max_in=batch * self.full, device=d["device"])
+        self.rspec, self.res = d.get("resample.spec"), None
+        self.rate = spec["rate"] if self.rspec is None else self.rspec["rate"]
+        self.per_block = spec["out_per_block"] if self.rspec is None else self.rspec["out_per_block"]
+        self.dem = Demodulator(spec["mode"], spec["decim"], taps, out_fmt="s16" if self.rspec is None else "f32",
+                               pcm_scale=DEMOD_PCM_SCALE, max_in=batch * self.full, device=d["device"])
+        if self.rspec is not None:                   # audioRate: float32 audio goes on to the resampler, which makes the int16
+            r = self.rspec
+            self.res = Resampler(r["L"], r["M"], resample_taps(r["L"], r["M"], r["taps_per_phase"]), type="f32", out_fmt="s16",
+                                 pcm_scale=DEMOD_PCM_SCALE, max_in=batch * r["in_per_block"], device=d["device"])
         self.parts = []
 
     def feed(self, iq_dev, got, stride=None):
         """iq_dev: [got][fullSize] complex64 in device memory, the down-converter's own buffer (or, with a stride in values,
         one channel of every block of the channelizer's)."""
         m = self.dem.blocks_dev(iq_dev, got, self.full, block_stride=stride)
-        self.parts.append(self.dem.read_out(got * m))
+        if self.res is None:
+            self.parts.append(self.dem.read_out(got * m))
+            return
+        j = self.res.blocks_dev(self.dem._out, got, m)     # both on the NULL stream: the demodulator's blocks come first
+        self.parts.append(self.res.read_out(got * j))
 
     def handoff(self, d):
         """The hand-off array, the INFO line, demodSave."""
         pcm = np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=np.int16)
-        d["demodAudio"], d["demodRate"] = pcm, self.spec["rate"]
+        d["demodAudio"], d["demodRate"] = pcm, self.rate
         print("INFO:zero_span: demod [{}]: [{}] samples at [{}] Hz, [{}] per block, peak [{}]".format(
-            self.spec["mode"], len(pcm), self.spec["rate"], self.spec["out_per_block"], int(np.abs(pcm.astype(np.int32)).max()) if len(pcm) else 0))
+            self.spec["mode"], len(pcm), self.rate, self.per_block, int(np.abs(pcm.astype(np.int32)).max()) if len(pcm) else 0))
         if d["demodSave"]:
-            write_wav(d["demodSave"], pcm, self.spec["rate"])
+            write_wav(d["demodSave"], pcm, self.rate)
 
     def close(self):
         self.dem.close()
+        if self.res is not None:
+            self.res.close()
 
 
 class _ChanFeed:
