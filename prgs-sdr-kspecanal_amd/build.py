@@ -1,4 +1,4 @@
-"""Build the shared libraries for gfx950 with hipcc, one translation unit each (PRODUCTS and MORE_PRODUCTS below).  In-tree, no
+"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of TABLES below).  In-tree, no
 JIT cache: every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's
 sources with -DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
 import os
@@ -25,6 +25,11 @@ PRODUCTS = {
 MORE_PRODUCTS = {
     "libksa_resamp.so": ("csrc_resamp", "krs_api.hip", "ksa_resamp.h", []),
 }
+# and the ones after the resampler; the next companion is one more entry here
+LATER_PRODUCTS = {
+    "libksa_corr.so": ("csrc_corr", "kcr_api.hip", "ksa_corr.h", []),
+}
+TABLES = [PRODUCTS, MORE_PRODUCTS, LATER_PRODUCTS]      # every product of every table is built, in this order
 OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 
@@ -37,7 +42,7 @@ def _files(subdir):
 def _sources(product):
     """Every file the product depends on: its directory, its header and, for a companion library, csrc_shared/ (which csrc/
     does not include)."""
-    subdir, _, header, _ = PRODUCTS[product] if product in PRODUCTS else MORE_PRODUCTS[product]
+    subdir, _, header, _ = next(table[product] for table in TABLES if product in table)
     shared = _files("csrc_shared") if subdir != "csrc" else []
     return _files(subdir) + shared + [os.path.join(HERE, "..", "include", header)]
 
@@ -46,25 +51,30 @@ def sources():
     return _sources("libksa.so")
 
 
-# product's path -> (the .hip that is compiled, extra flags, every file the product depends on)
-JOBS = {os.path.join(HERE, name): (os.path.join(HERE, subdir, hip), extra, lambda name=name: _sources(name))
-        for name, (subdir, hip, _, extra) in PRODUCTS.items()}
-MORE_JOBS = {os.path.join(HERE, name): (os.path.join(HERE, subdir, hip), extra, lambda name=name: _sources(name))
-             for name, (subdir, hip, _, extra) in MORE_PRODUCTS.items()}
+def _jobs(table):
+    """product's path -> (the .hip that is compiled, extra flags, every file the product depends on)"""
+    return {os.path.join(HERE, name): (os.path.join(HERE, subdir, hip), extra, lambda name=name: _sources(name))
+            for name, (subdir, hip, _, extra) in table.items()}
+
+
+JOBS = _jobs(PRODUCTS)
+MORE_JOBS = _jobs(MORE_PRODUCTS)
+LATER_JOBS = _jobs(LATER_PRODUCTS)
+JOB_TABLES = [JOBS, MORE_JOBS, LATER_JOBS]              # one per entry of TABLES
 
 
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(s) > t for s in (JOBS[out] if out in JOBS else MORE_JOBS[out])[2]())
+    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in JOB_TABLES if out in jobs)[2]())
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the libraries side by side, JOBS then MORE_JOBS).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the libraries side by side, the tables of JOB_TABLES in turn).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, (src, extra, _) in list(JOBS.items()) + list(MORE_JOBS.items()):
+    for out, (src, extra, _) in [job for table in JOB_TABLES for job in table.items()]:
         if not force and not is_stale(out):
             continue
         cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]

@@ -41,7 +41,12 @@ once, each at samplingRate x O / M, channel `pick` goes on to the engine (and to
 default empty = off), `channelsSave` (an .npz of power_db, freqs and the parameters) and `audioRate` (HZ[:tapsPerPhase],
 zeroSpan only, needs `demod`: the demodulator then leaves float32 audio on the GPU and a polyphase L / M resampler, L / M = HZ
 over the demodulator's rate, reduced, turns every block of it into int16 PCM at exactly HZ, which is what d['demodRate'] and the
-WAV header then say; default empty = off).
+WAV header then say; default empty = off) and `correlate` (FILE.npy[:threshold[:guard[:events=N]]], zeroSpan only, not with
+`zoom` or `channels`: a matched-filter correlator over every frame's raw block -- FILE holds a complex template [K] or a bank
+[Q][K]; every lag of every block gets its normalised correlation against each template, and the lags at which it peaks at or
+above threshold (default 0.5) within guard lags on either side (default K) are listed; handed off as d['corrEvents'] (block is
+the running block index of the run) and d['corrTotal']; default empty = off), `correlateSave` (an .npz of the events, toa =
+block, fractional position and seconds inside the block, and the parameters).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -74,6 +79,8 @@ from . import chan as _chan
 from .chan import Channelizer, chan_prototype, channel_freqs
 from . import resamp as _resamp
 from .resamp import Resampler, resample_taps, rate_ratio
+from . import corr as _corr
+from .corr import Correlator, refine
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -107,6 +114,7 @@ _KEYS = {
     "ZOOM": ("zoom", str), "DETECT": ("detect", str), "DETECTSAVE": ("detectSave", str),
     "DEMOD": ("demod", str), "DEMODSAVE": ("demodSave", str),
     "CHANNELS": ("channels", str), "CHANNELSSAVE": ("channelsSave", str), "AUDIORATE": ("audioRate", str),
+    "CORRELATE": ("correlate", str), "CORRELATESAVE": ("correlateSave", str),
 }
 
 
@@ -124,7 +132,7 @@ def defaults():
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
         "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
-        "audioRate": "",
+        "audioRate": "", "correlate": "", "correlateSave": "",
     }
 
 
@@ -212,6 +220,7 @@ def handle_args(d, argv=None):
     _handle_detect(d)
     _handle_demod(d)
     _handle_resample(d)
+    _handle_correlate(d)
     return d
 
 
@@ -460,6 +469,70 @@ def _handle_detect(d):
     if d["bUsePSD"]:
         prg_quit(d, "ERROR:handle_args: detect [{}] needs bUsePSD false: it reads the engine's own dB rows".format(text))
     d["detect.spec"] = spec
+
+
+CORR_RULE = ("correlate wants FILE.npy[:threshold[:guard[:events=N]]] with a finite 0 < threshold <= 1 (default 0.5), an integer "
+             "1 <= guard <= %d lags (default K, the template length) and 1 <= N <= %d events (default 4096)" % (
+                 _corr.MAX_GUARD, _corr.MAX_CAPACITY))
+CORR_FILE_RULE = ("a complex template [K] or bank [Q][K] with 1 <= K <= %d, 1 <= Q <= %d, Q x K <= %d, every value finite and no "
+                  "template all zero" % (_corr.MAX_K, _corr.MAX_Q, _corr.MAX_TEMPLATE_VALUES))
+
+
+def _handle_correlate(d):
+    """correlate FILE.npy[:threshold[:guard[:events=N]]] (additive, zeroSpan only): d['corr.spec'] = dict(file, templates,
+    threshold, guard, capacity), or None when the key is off."""
+    d["corr.spec"] = None
+    text = d["correlate"]
+    if not text:
+        if d["correlateSave"]:
+            print("WARN:handle_args: correlateSave [{}] is ignored without correlate".format(d["correlateSave"]))
+        return
+    spec = dict(file="", templates=None, threshold=0.5, guard=None, capacity=4096)
+    try:
+        parts = text.split(":")
+        if len(parts) > 4 or not parts[0]:
+            raise ValueError(text)
+        spec["file"] = parts[0]
+        if len(parts) > 1:
+            spec["threshold"] = float(parts[1])
+        if len(parts) > 2:
+            spec["guard"] = int(parts[2])
+        if len(parts) > 3:
+            name, eq, value = parts[3].partition("=")
+            if not eq or name.lower() != "events":
+                raise ValueError(text)
+            spec["capacity"] = int(value)
+        if not (np.isfinite(spec["threshold"]) and 0 < spec["threshold"] <= 1 and 1 <= spec["capacity"] <= _corr.MAX_CAPACITY
+                and (spec["guard"] is None or 1 <= spec["guard"] <= _corr.MAX_GUARD)):
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: correlate [{}]: {}".format(text, CORR_RULE))
+    try:
+        t = np.load(spec["file"], allow_pickle=False)
+        if not (isinstance(t, np.ndarray) and np.iscomplexobj(t) and t.ndim in (1, 2)):
+            raise ValueError(text)
+        t = np.ascontiguousarray(t.reshape(1, -1) if t.ndim == 1 else t, dtype=np.complex64)
+        q, k = t.shape
+        if not (1 <= k <= _corr.MAX_K and 1 <= q <= _corr.MAX_Q and q * k <= _corr.MAX_TEMPLATE_VALUES
+                and np.all(np.isfinite(t.view(np.float32))) and np.all(np.abs(t).max(axis=1) > 0)):
+            raise ValueError(text)
+    except (OSError, ValueError):
+        prg_quit(d, "ERROR:handle_args: correlate [{}]: the file [{}] must hold {}".format(text, spec["file"], CORR_FILE_RULE))
+    spec["templates"] = t
+    if spec["guard"] is None:
+        spec["guard"] = k
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: correlate [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: correlate [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["zoom"] or d["channels"]:
+        prg_quit(d, "ERROR:handle_args: correlate [{}] reads the raw blocks: correlating behind zoom or channels is out of scope, "
+                    "drop [{}]".format(text, "zoom" if d["zoom"] else "channels"))
+    if d["fullSize"] < k:
+        prg_quit(d, "ERROR:handle_args: correlate [{}]: a block of fullSize [{}] samples is shorter than the template of [{}]".format(
+            text, d["fullSize"], k))
+    d["corr.spec"] = spec
 
 
 DEMOD_PCM_SCALE = 32767.0                    # int16 per unit of the filtered detector: AM full scale 1, FM and PM one cycle
@@ -1082,9 +1155,11 @@ def zero_span(d):
     aspec = d.get("demod.spec") if front is not None else None
     audio = _DemodFeed(d, aspec, front, batch) if aspec is not None else None
     bank = _ChanFeed(d, cspec, batch) if cspec is not None else None
+    kspec = d.get("corr.spec") if sdr_curscan is _gpu_curscan else None
+    corr = _CorrFeed(d, kspec, batch) if kspec is not None else None
     try:
-        if batch > 1 or dens is not None or trig is not None or front is not None or det is not None:    # density, mask, zoom and detect run the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank)
+        if batch > 1 or dens is not None or trig is not None or front is not None or det is not None or corr is not None:    # density, mask, zoom, detect and correlate run the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank, corr)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
@@ -1097,7 +1172,11 @@ def zero_span(d):
             audio.handoff(d)
         if bank is not None:
             bank.handoff(d)
+        if corr is not None:
+            corr.handoff(d)
     finally:
+        if corr is not None:
+            corr.close()
         if audio is not None:
             audio.close()
         if bank is not None:
@@ -1215,6 +1294,51 @@ class _DetectFeed:
 
     def close(self):
         self.det.close()
+
+
+class _CorrFeed:
+    """The correlate key's state over a run: the Correlator, whose block form runs over every batch's raw blocks in their
+    iqFormat, read from the page-locked batch buffer; block numbers are frame numbers of the run."""
+
+    def __init__(self, d, spec, batch):
+        self.spec, self.full, self.rate = spec, d["fullSize"], d["samplingRate"]
+        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
+        self.corr = Correlator(spec["templates"], threshold=spec["threshold"], guard=spec["guard"], capacity=spec["capacity"],
+                               max_in=batch * self.full, fmt=fmt, device=d["device"])
+        self.blocks_done, self.stored, self.parts = 0, 0, []
+
+    def feed(self, blocks, got):
+        """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
+        self.corr.blocks_dev(blocks, got, self.full)
+        if self.stored < self.corr.capacity:
+            ev, _ = self.corr.events()               # synchronises: the buffer is free for the next batch
+            new = ev[self.stored:]
+            new["block"] += self.blocks_done
+            self.parts.append(new)
+            self.stored = len(ev)
+        else:
+            self.corr.synchronize()
+        self.blocks_done += got
+
+    def handoff(self, d):
+        """The hand-off arrays, the INFO line, correlateSave."""
+        _, total = self.corr.events()
+        ev = np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=_corr.EVENT_DTYPE)
+        d["corrEvents"], d["corrTotal"] = ev, total
+        best = float(ev["metric"].max()) if len(ev) else 0.0
+        print("INFO:zero_span: correlate blocks [{}], templates [{}] of [{}] samples, events stored [{}] / total [{}], best metric [{:.6f}]".format(
+            self.blocks_done, self.corr.Q, self.corr.K, len(ev), total, best))
+        if d["correlateSave"]:
+            frac = refine(ev)
+            toa = np.stack([ev["block"].astype(np.float64), frac, frac / self.rate], axis=1).reshape(-1, 3)
+            s = self.spec
+            with open(d["correlateSave"], "wb") as f:
+                np.savez(f, events=ev, events_total=np.int64(total), toa=toa, templates=s["templates"],
+                         threshold=np.float32(s["threshold"]), guard=np.int32(s["guard"]), capacity=np.int32(s["capacity"]),
+                         sampling_rate=np.float64(self.rate), block_len=np.int64(self.full))
+
+    def close(self):
+        self.corr.close()
 
 
 class _DemodFeed:
@@ -1342,7 +1466,7 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None, bank=None):
+def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None, bank=None, corr=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
@@ -1355,7 +1479,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
     page-locked memory as on the int8 / int16 route.  With demod the demodulator's block form runs over the same zoomed blocks
     (kdm_blocks_dev) and the batch's int16 audio is fetched with kdm_read_out.  With channels in place of zoom every block is
     the channelizer's block length, kch_blocks_dev leaves [got][M][fullSize] complex64 in its buffer, and the engine and the
-    demodulator read the picked channel of every block at a stride of M x fullSize values."""
+    demodulator read the picked channel of every block at a stride of M x fullSize values.  With correlate (never together with
+    a front end) the correlator's block form reads the batch's raw blocks from the same page-locked buffer (kcr_blocks_dev)."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
     full = zoom["block_len"] if zoom is not None else bank.spec["block_len"] if bank is not None else d["fullSize"]
     dtype, per = raw_dtype(u8)
@@ -1412,6 +1537,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
                     trig.feed(db)
                 if det is not None:
                     det.feed(db)
+            if got and corr is not None:
+                corr.feed(blocks, got)
             done += got
             if got < k:
                 prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)

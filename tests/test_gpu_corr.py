@@ -1,0 +1,526 @@
+"""The correlator on the GPU against tests/corr_model.py (whose float32 emulation and exact generators are checked on the CPU, in
+tests/test_corr_host.py).  Shapes (K, Q) take both plans (2048 lags per workgroup, eight per thread, for Q <= 2; 1024, four per
+thread, above), K below, at and not a multiple of the lags per thread, and the limits of K and of Q K.  Lag counts sit on every
+edge of the tile: 0, 1, 2, W-1, W, W+1, 3W+5, once from a pointer one sample into a 16-byte-aligned allocation, and every input
+format once.  Exact inputs are compared with np.array_equal, floats against the bound written down in corr_model."""
+import importlib
+import re
+
+import numpy as np
+import pytest
+
+import corr_model as cm
+from conftest import load_pkg
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (2, 1), (7, 3), (64, 1), (255, 2), (256, 8), (1024, 1), (4096, 1), (2048, 8)]
+EXACT_SHAPES = [s for s in SHAPES if s[0] <= 256]
+PLANT_SHAPES = [s for s in SHAPES if s[0] >= 64]      # below, a window of noise reaches rho 0.5 by chance (K = 1: rho is 1)
+WORST = {}
+
+
+def tile_of(shape):
+    return 2048 if shape[1] <= 2 else 1024
+
+
+def guards_of(shape):
+    return sorted({1, 5, shape[0]})
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return torch
+
+
+@pytest.fixture(scope="module")
+def X():
+    load_pkg()
+    return importlib.import_module("prgs-sdr-kspecanal_amd.corr")
+
+
+def to_dev(torch, raw, offset=0):
+    """(tensor that owns the memory, device address of the samples): raw is complex64 [n] or an integer array [n][2]; `offset`
+    samples into a 16-byte-aligned allocation."""
+    raw = np.ascontiguousarray(raw)
+    per = 8 if raw.dtype == np.complex64 else 2 * raw.dtype.itemsize
+    b = raw.view(np.uint8).reshape(-1)
+    buf = torch.zeros(len(b) + per * offset + 16, dtype=torch.uint8, device="cuda")
+    if len(b):
+        buf[per * offset:per * offset + len(b)] = torch.from_numpy(b.copy())
+    assert buf.data_ptr() % 16 == 0
+    return buf, buf.data_ptr() + per * offset
+
+
+class Dense:
+    """Device buffers for the dense outputs of Q rows of `stride` lags."""
+
+    def __init__(self, torch, rows, stride):
+        self.rows, self.stride = rows, max(int(stride), 1)
+        self.metric = torch.full((rows * self.stride,), -7.0, dtype=torch.float32, device="cuda")
+        self.corr = torch.full((rows * self.stride * 2,), -7.0, dtype=torch.float32, device="cuda")
+
+    def at(self, done):
+        return self.metric.data_ptr() + 4 * done, self.corr.data_ptr() + 8 * done
+
+    def fetch(self, lags):
+        rho = self.metric.cpu().numpy().reshape(self.rows, self.stride)
+        r = self.corr.cpu().numpy().view(np.complex64).reshape(self.rows, self.stride)
+        assert np.all(rho[:, lags:] == -7.0), "nothing is written past the lags of the call"
+        return rho[:, :lags].copy(), r[:, :lags].copy()
+
+
+def run_stream(torch, cr, raw, pieces=None, offset=0, flush=True):
+    """raw through process_dev in pieces (None: whole) into a caller's buffers; returns (rho, r, events, total)."""
+    n = len(raw)
+    lags = cm.lags_after(n, cr.K)
+    out = Dense(torch, cr.Q, lags)
+    keep, ptr = to_dev(torch, raw, offset)
+    per = 8 if raw.dtype == np.complex64 else 2 * raw.dtype.itemsize
+    at = done = 0
+    for p in ([n] if pieces is None else pieces):
+        want = cr.out_count(p)
+        m, c = out.at(done)
+        got = cr.process_dev(ptr + per * at if p else 0, p, metric=m, corr=c, out_stride=out.stride)
+        assert got == want == cm.out_count(at, p, cr.K)
+        at, done = at + p, done + got
+    assert at == n and done == lags
+    st = cr.state()
+    assert st == {"samples_in": n, "lags_done": lags, "lags_decided": max(0, lags - cr.guard)}
+    if flush:
+        cr.flush()
+        assert cr.state()["lags_decided"] == lags
+    ev, total = cr.events()
+    rho, r = out.fetch(lags)
+    return rho, r, ev, total
+
+
+def events_equal(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and all(np.array_equal(a[k], b[k]) for k in a.dtype.names)
+
+
+def rand_c64(rng, n):
+    return (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(np.complex64)
+
+
+def rand_templates(rng, Q, K):
+    return np.exp(2j * np.pi * rng.uniform(0, 1, (Q, K))).astype(np.complex64)
+
+
+# ------------------------------------------------------------------------------------------ 1. impulse
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_unit_impulse_reads_the_conjugate_template_back(X, torch_cuda, shape):
+    K, Q = shape
+    rng = np.random.default_rng(100 + K + Q)
+    c = (rng.standard_normal((Q, K)) + 1j * rng.standard_normal((Q, K))).astype(np.complex64)
+    s = K + 37
+    x = np.zeros(2 * K + 90, dtype=np.complex64)
+    x[s] = 1
+    cr = X.Correlator(c, guard=1, max_in=len(x))
+    rho, r = cr.process(x)                                           # host to host
+    cr.close()
+    lags = len(x) - K + 1
+    assert rho.shape == r.shape == (Q, lags)
+    want = np.zeros((Q, lags), dtype=np.complex64)
+    for n in range(s - K + 1, s + 1):
+        want[:, n] = np.conj(c[:, s - n])
+    assert np.array_equal(r, want)
+    ec = cm.ec32(c)
+    p = (want.real * want.real + want.imag * want.imag)              # one tap: |c|^2 over 1 * Ec
+    assert np.all(rho[:, :s - K + 1] == 0) and np.all(rho[:, s + 1:] == 0)
+    assert np.allclose(rho, p / ec[:, None], rtol=1e-6, atol=0)
+
+
+# ------------------------------------------------------------------------------------------ 2. exact
+def exact_stream(shape, G, n):
+    """Integer samples: noise, copies of the templates back to back and further apart (rho = 1 at lags K, K + 1, K + G, ... from
+    each other: inside and outside G), a stretch of zeros (windows of no energy), and, for K > 2, a last template of period two
+    with a stretch of the same period in the samples, where rho = 1 at every second lag (the tie rule at every G)."""
+    K, Q = shape
+    rng = np.random.default_rng(K * 1000 + Q * 10 + G)
+    c = cm.exact_templates(rng, Q, K)
+    pattern = np.array([1, 1j], dtype=np.complex64)
+    if K > 2:
+        c[Q - 1] = pattern[np.arange(K) % 2]
+    x = cm.exact_samples(rng, n)
+    at = 3
+    for i, gap in enumerate((0, 1, G, 2 * G + 3, 0)):
+        if at + K > n // 2:
+            break
+        x[at:at + K] = (1 + (i % 3)) * c[i % Q]
+        at += K + gap
+    x[n // 2:n // 2 + K + 3 + G] = 0                                 # K = 1: the one place where G lags in a row are below 1
+    first, m = n // 2 + K + G + 10, K + 2 * G + 6
+    if K > 2 and first + m <= n:
+        x[first:first + m] = 2 * pattern[np.arange(m) % 2]
+    return c, x
+
+
+@pytest.mark.parametrize("shape", EXACT_SHAPES, ids=str)
+def test_exact_inputs_match_the_model_bit_for_bit(X, torch_cuda, shape):
+    K, Q = shape
+    W = tile_of(shape)
+    for G in guards_of(shape):
+        full = 3 * W + 5 + K - 1
+        c, x = exact_stream(shape, G, full)
+        rho_all, r_all = cm.exact_model(x, c)
+        cr = X.Correlator(c, threshold=0.5, guard=G, capacity=1 << 16, max_in=full + 8)
+        info = cr.kernel_info()
+        assert info["tile_out"] == W and info["threads"] == 256
+        for lags in (0, 1, 2, W - 1, W, W + 1, 3 * W + 5):
+            n = lags + K - 1
+            cr.reset()
+            rho, r, ev, total = run_stream(torch_cuda, cr, x[:n], offset=1 if (lags == W + 1 and G == 5) else 0)
+            assert np.array_equal(rho, rho_all[:, :lags]) and np.array_equal(r, r_all[:, :lags]), (G, lags)
+            want = cm.records(rho_all[:, :lags], r_all[:, :lags], 0.5, G)
+            assert total == len(want) and events_equal(ev, want), (G, lags)
+        assert len(want) >= 2 and (want["metric"] == 1).sum() >= 2, "the planted copies must be found"
+        # other thresholds, min_energy on: from the next call
+        for thr, me in ((0.25, 0.0), (1.0, 0.0), (0.3, 12.0 * K)):
+            cr.set_params(threshold=thr, min_energy=me)
+            cr.reset()
+            rho, r, ev, total = run_stream(torch_cuda, cr, x)
+            want_rho, want_r = cm.exact_model(x, c, me)
+            assert np.array_equal(rho, want_rho) and np.array_equal(r, want_r)
+            want = cm.records(want_rho, want_r, thr, G)
+            assert total == len(want) and events_equal(ev, want), (G, thr, me)
+            assert me == 0 or ((want_rho == 0) & (rho_all > 0)).any(), "min_energy must silence some window"
+        cr.close()
+
+
+@pytest.mark.parametrize("fmt", ["c64", "u8", "s8", "s16"])
+def test_every_input_format_exactly(X, torch_cuda, fmt):
+    shape, G = (7, 3), 5
+    K, Q = shape
+    W = tile_of(shape)
+    c, x = exact_stream(shape, G, W + 1 + K - 1)
+    ints = np.stack([x.real, x.imag], axis=1)
+    # u8 with offset 128 and scale 1 is the integer itself; int8 is the integer over 2^7, int16 over 2^15: powers of two, so
+    # r scales exactly and rho, a ratio, is unchanged
+    raw, scale = {"c64": (x, 1.0), "u8": ((ints + 128).astype(np.uint8), 1.0), "s8": (ints.astype(np.int8), 2.0 ** -7),
+                  "s16": (ints.astype(np.int16), 2.0 ** -15)}[fmt]
+    cr = X.Correlator(c, threshold=0.5, guard=G, capacity=4096, max_in=len(x), fmt=fmt, u8_offset=128.0, u8_scale=1.0)
+    rho, r, ev, total = run_stream(torch_cuda, cr, raw, offset=1)    # the integer formats from a misaligned start, too
+    want_rho, want_r = cm.exact_model(x, c)
+    want_r = (want_r * np.float32(scale)).astype(np.complex64)
+    assert np.array_equal(rho, want_rho) and np.array_equal(r, want_r)
+    want = cm.records(want_rho, want_r, 0.5, G)
+    assert total == len(want) > 0 and events_equal(ev, want)
+    # the host form unpacks the same
+    cr.reset()
+    rho2, r2 = cr.process(raw)
+    assert np.array_equal(rho2, rho) and np.array_equal(r2, r)
+    cr.close()
+
+
+# ------------------------------------------------------------------------------------------ 3. float
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_random_floats_stay_inside_the_bound(X, torch_cuda, shape):
+    K, Q = shape
+    W = tile_of(shape)
+    lags = 3 * W + 5 if K <= 256 else W + 1
+    rng = np.random.default_rng(300 + K * 7 + Q)
+    c = (rng.uniform(-1, 1, (Q, K)) + 1j * rng.uniform(-1, 1, (Q, K))).astype(np.complex64)
+    x = rand_c64(rng, lags + K - 1)
+    cr = X.Correlator(c, threshold=1.0, guard=1, max_in=len(x))
+    rho, r, _, _ = run_stream(torch_cuda, cr, x)
+    cr.close()
+    w_rho, w_r = cm.worst_ratios(rho, r, x, c)
+    WORST[shape] = (w_rho, w_r)
+    print("correlator %s: rho error / bound %.4f, r error / bound %.4f" % (shape, w_rho, w_r))
+    assert w_rho <= 1.0 and w_r <= 1.0, (shape, w_rho, w_r)
+
+
+def planted_stream(shape, G, seed=0):
+    """Copies of the templates, scaled and rotated, in noise 20 dB below them, at known lags at least max(2G + 2, K) apart."""
+    K, Q = shape
+    rng = np.random.default_rng(4000 + K + 13 * Q + G + seed)
+    c = rand_templates(rng, Q, K)                                    # unit modulus: power 1 per sample
+    step = max(2 * G + 2, K) + 17
+    where = [(40 + i * step, i % Q) for i in range(5)]
+    n = where[-1][0] + 2 * K + G + 50
+    x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)) * np.sqrt(0.01 / 2)
+    for i, (s, q) in enumerate(where):
+        x[s:s + K] += (1.0 + 0.4 * i) * np.exp(2j * np.pi * rng.uniform()) * c[q]
+    return c, x.astype(np.complex64), where
+
+
+@pytest.mark.parametrize("shape", PLANT_SHAPES, ids=str)
+def test_planted_copies_are_found_and_nothing_else(X, torch_cuda, shape):
+    K, Q = shape
+    for G in guards_of(shape):
+        c, x, where = planted_stream(shape, G)
+        # on the CPU model first, with margin: these inputs alone give exactly the planted lags
+        rho64, _ = cm.definition(x, c)
+        for thr in (0.4, 0.5):
+            found = sorted((p, q) for q in range(Q) for p in cm.peaks(rho64[q], thr, G))
+            assert found == where, (G, thr)
+        assert min(rho64[q, s] for s, q in where) > 0.95
+        cr = X.Correlator(c, threshold=0.5, guard=G, max_in=len(x))
+        rho, r, ev, total = run_stream(torch_cuda, cr, x)
+        cr.close()
+        assert total == len(where) and [(int(e["pos"]), int(e["templ"])) for e in ev] == where, G
+        assert np.all(ev["metric"] > 0.9) and np.all(ev["block"] == -1)
+        assert events_equal(ev, cm.records(rho, r, 0.5, G))         # every field follows from the dense values
+
+
+# ------------------------------------------------------------------------------------------ 4. cut independence
+@pytest.mark.parametrize("shape,G,ones", [((7, 3), 5, True), ((64, 1), 64, False), ((256, 8), 1, False), ((1024, 1), 5, False)], ids=str)
+def test_the_cut_of_a_stream_is_invisible(X, torch_cuda, shape, G, ones):
+    K, Q = shape
+    W = tile_of(shape)
+    n = 3 * W + K + 11
+    rng = np.random.default_rng(500 + K)
+    c = rand_templates(rng, Q, K)
+    x = rand_c64(rng, n) * np.float32(0.1)
+    for i, s in enumerate(range(5, n - K, max(n // 7, K + 2 * G + 3))):      # peaks near the cuts and the tile edges
+        x[s:s + K] += c[i % Q]
+    cr = X.Correlator(c, threshold=0.5, guard=G, max_in=n)
+    whole = run_stream(torch_cuda, cr, x)
+    assert whole[3] >= 3 and events_equal(whole[2], cm.records(whole[0], whole[1], 0.5, G))
+    with pytest.raises(X.KsaError, match="flushed"):
+        cr.process_dev(0, 0)
+    with pytest.raises(X.KsaError, match="flushed"):
+        cr.flush()
+    assert cr.state()["samples_in"] == n
+
+    def cut(size):
+        sizes = [size] * (n // size)
+        return sizes + ([n - sum(sizes)] if n - sum(sizes) else [])
+
+    cuts = [cut(s) for s in sorted({2, max(K - 1, 1), K, 997})]
+    if ones:
+        cuts.append([1] * n)
+    r2 = np.random.default_rng(K)
+    rnd = []
+    while sum(rnd) < n:
+        rnd.append(int(min(r2.integers(0, 2 * K + 50), n - sum(rnd))))
+    cuts.append(rnd)
+    for pieces in cuts:
+        cr.reset()                                                   # allowed again after reset
+        got = run_stream(torch_cuda, cr, x, pieces, flush=False)
+        decided = max(0, n - K + 1 - G)
+        before = cm.records(whole[0], whole[1], 0.5, G, last=decided)
+        assert got[3] == len(before) and events_equal(got[2], before), "the tail is undecided before flush"
+        cr.flush()
+        ev, total = cr.events()
+        assert np.array_equal(got[0], whole[0]) and np.array_equal(got[1], whole[1]), pieces[:3]
+        assert total == whole[3] and events_equal(ev, whole[2]), pieces[:3]
+    cr.close()
+
+
+# ------------------------------------------------------------------------------------------ 5. block and stream
+@pytest.mark.parametrize("shape,G", [((7, 3), 5), ((64, 1), 1), ((1024, 1), 1024)], ids=str)
+def test_blocks_cut_from_a_stream_equal_the_stream(X, torch_cuda, shape, G):
+    K, Q = shape
+    rng = np.random.default_rng(600 + K)
+    c = rand_templates(rng, Q, K)
+    block_len, stride, nb = K + 150, 37, 5
+    n = (nb - 1) * stride + block_len
+    x = rand_c64(rng, n) * np.float32(0.1)
+    for i, s in enumerate(range(3 + 2 * stride, n - K, max(61, K + 30))):     # the first copy lies in blocks 0, 1 and 2
+        x[s:s + K] += c[i % Q] * np.float32(0.5)
+    cr = X.Correlator(c, threshold=0.3, guard=G, max_in=nb * block_len)
+    s_rho, s_r, _, _ = run_stream(torch_cuda, cr, x)
+    keep, ptr = to_dev(torch_cuda, x)
+    nl = block_len - K + 1
+    for st, ostride in ((stride, nl + 9), (0, nl), (block_len, nl)):
+        blocks = nb if st != block_len else 1
+        cr.clear_events()
+        out = Dense(torch_cuda, blocks * Q, ostride)
+        assert cr.blocks_dev(ptr, blocks, block_len, block_stride=st, metric=out.metric, corr=out.corr, out_stride=ostride) == nl
+        rho, r = out.fetch(nl)
+        rho, r = rho.reshape(blocks, Q, nl), r.reshape(blocks, Q, nl)
+        for b in range(blocks):
+            assert np.array_equal(rho[b], s_rho[:, b * st:b * st + nl]) and np.array_equal(r[b], s_r[:, b * st:b * st + nl]), (st, b)
+        ev, total = cr.events()
+        want = cm.block_records(rho, r, 0.3, G)
+        assert total == len(want) >= (3 if st == stride else blocks) and events_equal(ev, want), st
+        key = [(int(e["block"]), int(e["pos"]), int(e["templ"])) for e in ev]
+        assert key == sorted(key) and len(set(key)) == len(key)
+    assert cr.state()["samples_in"] == n, "the block form leaves the stream state alone"
+    cr.close()
+
+
+# ------------------------------------------------------------------------------------------ 6. capacity and parameters
+def test_capacity_counts_and_parameters(X, torch_cuda):
+    K, Q, G = 64, 1, 5
+    rng = np.random.default_rng(77)
+    c = rand_templates(rng, Q, K)
+    where = [30 + 100 * i for i in range(10)]
+    x = np.zeros(where[-1] + K + 40, dtype=np.complex64)
+    for i, s in enumerate(where):
+        x[s:s + K] = (1 + i) * c[0]
+    x += rand_c64(rng, len(x)) * np.float32(1e-3)
+    cr = X.Correlator(c, threshold=0.5, guard=G, capacity=3, max_in=len(x))
+    keep, ptr = to_dev(torch_cuda, x)
+    half = where[5] + 7
+    cr.process_dev(ptr, half)
+    ev, total = cr.events()
+    assert total == 5 and list(ev["pos"]) == where[:3]
+    cr.process_dev(ptr + 8 * half, len(x) - half)
+    cr.flush()
+    ev, total = cr.events()
+    assert total == 10 and list(ev["pos"]) == where[:3] and np.all(ev["metric"] > 0.99)
+    cr.clear_events()
+    assert cr.events()[1] == 0 and len(cr.events()[0]) == 0 and cr.state()["samples_in"] == len(x)
+    cr.reset()
+    assert cr.state() == {"samples_in": 0, "lags_done": 0, "lags_decided": 0} and cr.events()[1] == 0
+    # set_params and set_templates take effect from the next call
+    cr.blocks_dev(ptr, 1, len(x))
+    assert cr.events()[1] == 10
+    cr.clear_events()
+    cr.set_params(min_energy=1e9)
+    cr.blocks_dev(ptr, 1, len(x))
+    assert cr.events()[1] == 0
+    cr.set_params(min_energy=0.0, threshold=1e-6)
+    cr.blocks_dev(ptr, 1, len(x))
+    assert cr.events()[1] > 10 and len(cr.events()[0]) == 3
+    cr.clear_events()
+    cr.set_params(threshold=0.5)
+    other = rand_templates(np.random.default_rng(78), Q, K)
+    cr.set_templates(other)
+    cr.blocks_dev(ptr, 1, len(x))
+    assert cr.events()[1] == 0
+    cr.set_templates(c * np.float32(3))                              # rho does not depend on the template's scale
+    cr.blocks_dev(ptr, 1, len(x))
+    ev, total = cr.events()
+    assert total == 10 and list(ev["pos"]) == where[:3] and list(ev["block"]) == [0, 0, 0]
+    with pytest.raises(X.KsaError, match="set_templates wants"):
+        cr.set_templates(np.ones(K + 1, dtype=np.complex64))
+    cr.close()
+
+
+# ------------------------------------------------------------------------------------------ 7. refusals per call
+def test_refused_calls_leave_the_object_as_it_was(X, torch_cuda):
+    K, Q, G = 16, 2, 3
+    rng = np.random.default_rng(88)
+    c = rand_templates(rng, Q, K)
+    x = rand_c64(rng, 200) * np.float32(0.05)
+    x[50:50 + K] += c[1]
+    cr = X.Correlator(c, threshold=0.5, guard=G, max_in=256)
+    keep, ptr = to_dev(torch_cuda, x)
+    cr.process_dev(ptr, 120)
+    state, (ev, total) = cr.state(), cr.events()
+    assert total == 1
+    out = Dense(torch_cuda, Q, 64)
+    m, co = out.at(0)
+    lib, h = X.lib(), cr._h
+    texts = []
+    for call, text in ((lambda: cr.process_dev(ptr + 4, 8), "not aligned to the 8 bytes"), (lambda: cr.process_dev(ptr, -1), "n_in -1 must be >= 0"),
+                       (lambda: cr.process_dev(ptr, 257), "exceeds max_in 256"), (lambda: cr.process_dev(0, 8), "null input pointer"),
+                       (lambda: cr.process_dev(ptr, 80, metric=m, out_stride=79), "out_stride 79 is shorter than the 80 lags"),
+                       (lambda: cr.process_dev(ptr, 80, corr=co, out_stride=-1), "out_stride -1 is shorter"),
+                       (lambda: cr.process(np.zeros(300, dtype=np.complex64)), "exceeds max_in"),
+                       (lambda: cr.out_count(-1), "n_in -1 must be >= 0"),
+                       (lambda: cr.blocks_dev(ptr, 1, K - 1), "block_len 15 is shorter than the template of 16"),
+                       (lambda: cr.blocks_dev(ptr, -1, 32), "nblocks -1 must be >= 0"),
+                       (lambda: cr.blocks_dev(ptr, 2, 32, block_stride=-1), "block_stride -1 must be >= 0"),
+                       (lambda: cr.blocks_dev(ptr, 9, 32), "9 blocks of 32 samples exceed max_in 256"),
+                       (lambda: cr.blocks_dev(0, 2, 32), "null input pointer"), (lambda: cr.blocks_dev(ptr + 2, 2, 32), "not aligned"),
+                       (lambda: cr.blocks_dev(ptr, 2, 32, metric=m, out_stride=16), "out_stride 16 is shorter than the 17 lags of a block"),
+                       (lambda: cr.set_params(threshold=0.0), "threshold 0"), (lambda: cr.set_params(min_energy=-1.0), "min_energy -1"),
+                       (lambda: cr.set_templates(np.zeros((Q, K), dtype=np.complex64)), "template 0 has zero energy"),
+                       (lambda: X.check(lib.kcr_set_templates(h, None)), "null templates"),
+                       (lambda: X.check(lib.kcr_read_events(h, None, -1, None, None)), "max_records -1"),
+                       (lambda: X.check(lib.kcr_read_events(h, None, 0, None, None)), "null records, stored and total"),
+                       (lambda: X.check(lib.kcr_events_dev(h, None, None)), "null records and events_total"),
+                       (lambda: X.check(lib.kcr_out_count(h, 1, None)), "null n_lags")):
+        with pytest.raises(X.KsaError) as e:
+            call()
+        assert text in str(e.value), (text, str(e.value))
+        texts.append(re.sub(r"-?[0-9][0-9.e+]*", "#", str(e.value)))
+        now, (ev2, total2) = cr.state(), cr.events()
+        assert now == state and total2 == total and events_equal(ev2, ev), text
+    assert len(set(texts)) >= 18, sorted(set(texts))
+    assert np.all(out.metric.cpu().numpy() == -7.0), "a refused call writes nothing"
+    cr.process_dev(ptr + 8 * 120, 80)                                # and the stream goes on as if nothing had been asked
+    cr.flush()
+    whole = X.Correlator(c, threshold=0.5, guard=G, max_in=256)
+    _, _, want, _ = run_stream(torch_cuda, whole, x)
+    assert events_equal(cr.events()[0], want)
+    whole.close()
+    cr.close()
+
+
+# ------------------------------------------------------------------------------------------ 8. kernel_info
+def test_the_plan_is_a_function_of_k_and_q_alone(X, torch_cuda):
+    rng = np.random.default_rng(9)
+    for K, Q in SHAPES:
+        c = rand_templates(rng, Q, K)
+        infos = []
+        for G, cap, max_in, fmt in ((1, 1, K + 5, "c64"), (min(K, 4096), 4096, 3 * K + 7000, "s16")):
+            cr = X.Correlator(c, guard=G, capacity=cap, max_in=max_in, fmt=fmt)
+            before = cr.kernel_info()
+            cr.process(np.zeros((K + 4, 2), dtype=np.int16) if fmt == "s16" else np.zeros(K + 4, dtype=np.complex64))
+            after = cr.kernel_info()
+            assert after["grid"] == 1 and before["grid"] >= 256
+            assert {k: v for k, v in before.items() if k != "grid"} == {k: v for k, v in after.items() if k != "grid"}
+            infos.append(after)
+            cr.close()
+        assert infos[0] == infos[1], (K, Q)
+        R = tile_of((K, Q)) // 256
+        assert infos[0]["tile_out"] == 256 * R and infos[0]["threads"] == 256
+        assert infos[0]["lds_bytes"] == 8 * R * (256 + -(-K // R) + 1)
+        # 64 KiB of LDS is the workgroup limit; 256 registers let two workgroups share a compute unit (512 per lane and SIMD),
+        # so that one loads its span while the other multiplies
+        assert infos[0]["lds_bytes"] <= 64 * 1024 and 0 < infos[0]["vgprs"] <= 256
+        print("correlator plan K %d Q %d: %s" % (K, Q, infos[0]))
+
+
+# ------------------------------------------------------------------------------------------ 9. the command line
+def band_limited(rng, K, tones=12, width=0.08):
+    """A Hann-windowed sum of tones within +-width cycles per sample, as a function of continuous time t in [0, K)."""
+    f, a = rng.uniform(-width, width, tones), np.exp(2j * np.pi * rng.uniform(0, 1, tones))
+
+    def wave(t):
+        t = np.asarray(t, dtype=np.float64)
+        w = np.where((t >= 0) & (t <= K), 0.5 - 0.5 * np.cos(2 * np.pi * t / K), 0.0)
+        return w * (a[None, :] * np.exp(2j * np.pi * f[None, :] * t[:, None])).sum(axis=1) / np.sqrt(tones)
+
+    return wave
+
+
+def test_cli_correlate_reports_and_saves(X, torch_cuda, tmp_path, capsys):
+    Kmod = importlib.import_module("prgs-sdr-kspecanal_amd.kspecanal")
+    K, frames, rate = 128, 5, 2048000
+    rng = np.random.default_rng(2024)
+    wave = band_limited(rng, K)
+    tmpl = wave(np.arange(K)).astype(np.complex64)
+    tfile, save, capture = tmp_path / "tmpl.npy", tmp_path / "out.npz", tmp_path / "capture.s16"
+    np.save(tfile, tmpl)
+    common = ["zeroSpan", "fftSize", "1024", "samplingRate", str(rate), "iqFormat", "s16", "bPltLevels", "false", "bPltHeatMap", "false",
+              "prgLoopCnt", str(frames), "frameBatch", "2"]
+    full = Kmod.handle_args({}, common)["fullSize"]
+    want_read = int(2 ** np.ceil(np.log2(full)))                     # what one block consumes of the capture
+    settle = 16 * 1024
+    x = (rng.standard_normal((frames, want_read)) + 1j * rng.standard_normal((frames, want_read))) * 0.01
+    # three bursts: two on whole samples, one half a sample late (band-limited, so it is the same waveform between the samples)
+    planted = [(0, 100, 0.0), (2, full - K - 1, 0.0), (4, 700, 0.5)]
+    for b, s, frac in planted:
+        x[b, s:s + K + 1] += 0.5 * wave(np.arange(K + 1) - frac)
+    iq = np.zeros((settle + frames * want_read, 2), dtype=np.int16)
+    flat = x.reshape(-1)
+    iq[settle:, 0], iq[settle:, 1] = np.rint(flat.real * 32768 * 0.25), np.rint(flat.imag * 32768 * 0.25)
+    iq.tofile(capture)
+    Kmod.sdr_curscan = Kmod._gpu_curscan
+    capsys.readouterr()
+    d = Kmod.main(common + ["source", "file:%s" % capture, "correlate", "%s:0.5:%d" % (tfile, K), "correlateSave", str(save)])
+    out = capsys.readouterr().out
+    ev = d["corrEvents"]
+    assert d["corrTotal"] == 3 == len(ev) and ev.dtype == X.EVENT_DTYPE
+    assert [(int(e["block"]), int(e["pos"])) for e in ev[:2]] == [(0, 100), (2, full - K - 1)]
+    assert int(ev[2]["block"]) == 4 and int(ev[2]["pos"]) in (700, 701) and np.all(ev["metric"] > 0.9) and np.all(ev["templ"] == 0)
+    toa = X.refine(ev)
+    assert abs(toa[0] - 100) < 0.1 and abs(toa[1] - (full - K - 1)) < 0.1 and abs(toa[2] - 700.5) < 0.1, toa
+    assert re.search(r"^INFO:zero_span: correlate blocks \[5\], templates \[1\] of \[128\] samples, events stored \[3\] / total \[3\], "
+                     r"best metric \[0\.9\d+\]", out, flags=re.M), out[-600:]
+    z = np.load(save)
+    assert sorted(z.files) == ["block_len", "capacity", "events", "events_total", "guard", "sampling_rate", "templates", "threshold", "toa"]
+    assert events_equal(z["events"], ev) and int(z["events_total"]) == 3 and z["toa"].shape == (3, 3)
+    assert np.array_equal(z["toa"][:, 0], [0, 2, 4]) and np.array_equal(z["toa"][:, 1], toa)
+    assert np.allclose(z["toa"][:, 2], toa / rate, rtol=1e-12, atol=0)
+    assert (float(z["threshold"]), int(z["guard"]), int(z["capacity"]), int(z["block_len"])) == (0.5, K, 4096, full)
+    assert np.array_equal(z["templates"], tmpl[None, :]) and float(z["sampling_rate"]) == rate
