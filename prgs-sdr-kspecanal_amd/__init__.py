@@ -10,7 +10,8 @@ digital down-converter (zoom) in front of the engine: mixer, low-pass and decima
 (chan.py) is the polyphase channelizer between the two: all M channels of a band at once, in libksa_chan.so; Resampler
 (resamp.py) is the rational L / M resampler behind any of them: real or complex samples at L / M times the rate, in
 libksa_resamp.so; Correlator (corr.py) is the matched-filter correlator and peak list over the raw samples: where in time a
-known waveform lies, in libksa_corr.so.
+known waveform lies, in libksa_corr.so; PulseDetector (pulse.py) is the time-domain pulse detector and pulse list over the raw
+samples: when something was on the air, in libksa_pulse.so.
 """
 from ._lib import KsaError, lib, LIB_PATH, FMT_C64, FMT_U8, FMT_S8, FMT_S16, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS, CUMU_PFB, CUMU_PFB_PSD
 from .engine import (SpectrumEngine, PinnedBuffer, allreduce_state, scan_allstitch, scan_gather_state, full_size_for,
@@ -24,6 +25,7 @@ from .demod import Demodulator, demod_taps, write_wav
 from .chan import Channelizer, chan_prototype, channel_freqs
 from .resamp import Resampler, resample_taps, rate_ratio
 from .corr import Correlator, frequency_bank, refine
+from .pulse import PulseDetector, PULSE_DTYPE, FLAG_OPEN_END, POWER_UNIT
 
 __all__ = ["KsaError", "SpectrumEngine", "lib", "LIB_PATH", "FMT_C64", "FMT_U8", "FMT_S8", "FMT_S16", "OUT_LINEAR", "OUT_DB",
            "OUT_DB_CLIP", "HM_ROWS", "PinnedBuffer", "allreduce_state", "scan_allstitch", "scan_gather_state", "full_size_for", "window_starts", "window_table", "heatmap_width",
@@ -31,4 +33,4 @@ __all__ = ["KsaError", "SpectrumEngine", "lib", "LIB_PATH", "FMT_C64", "FMT_U8",
            "SpectrumMask", "learn_mask", "DownConverter", "ddc_lowpass", "phase_inc_for",
            "SignalDetector", "EMISSION_DTYPE", "emission_freqs", "Demodulator", "demod_taps", "write_wav",
            "Channelizer", "chan_prototype", "channel_freqs", "Resampler", "resample_taps", "rate_ratio",
-           "Correlator", "frequency_bank", "refine"]
+           "Correlator", "frequency_bank", "refine", "PulseDetector", "PULSE_DTYPE", "FLAG_OPEN_END", "POWER_UNIT"]

@@ -1,4 +1,4 @@
-"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of TABLES below).  In-tree, no
+"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of ALL_TABLES below).  In-tree, no
 JIT cache: every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's
 sources with -DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
 import os
@@ -29,7 +29,12 @@ MORE_PRODUCTS = {
 LATER_PRODUCTS = {
     "libksa_corr.so": ("csrc_corr", "kcr_api.hip", "ksa_corr.h", []),
 }
-TABLES = [PRODUCTS, MORE_PRODUCTS, LATER_PRODUCTS]      # every product of every table is built, in this order
+TABLES = [PRODUCTS, MORE_PRODUCTS, LATER_PRODUCTS]      # the tables up to the correlator, in this order
+# the pulse detector, in a table of its own: the three above and TABLES stay as they were
+PULSE_PRODUCTS = {
+    "libksa_pulse.so": ("csrc_pulse", "kpl_api.hip", "ksa_pulse.h", []),
+}
+ALL_TABLES = TABLES + [PULSE_PRODUCTS]                  # every product of every table is built, in this order
 OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 
@@ -42,7 +47,7 @@ def _files(subdir):
 def _sources(product):
     """Every file the product depends on: its directory, its header and, for a companion library, csrc_shared/ (which csrc/
     does not include)."""
-    subdir, _, header, _ = next(table[product] for table in TABLES if product in table)
+    subdir, _, header, _ = next(table[product] for table in ALL_TABLES if product in table)
     shared = _files("csrc_shared") if subdir != "csrc" else []
     return _files(subdir) + shared + [os.path.join(HERE, "..", "include", header)]
 
@@ -61,20 +66,22 @@ JOBS = _jobs(PRODUCTS)
 MORE_JOBS = _jobs(MORE_PRODUCTS)
 LATER_JOBS = _jobs(LATER_PRODUCTS)
 JOB_TABLES = [JOBS, MORE_JOBS, LATER_JOBS]              # one per entry of TABLES
+PULSE_JOBS = _jobs(PULSE_PRODUCTS)
+ALL_JOB_TABLES = JOB_TABLES + [PULSE_JOBS]              # one per entry of ALL_TABLES
 
 
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in JOB_TABLES if out in jobs)[2]())
+    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in ALL_JOB_TABLES if out in jobs)[2]())
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the libraries side by side, the tables of JOB_TABLES in turn).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the libraries side by side, the tables of ALL_JOB_TABLES in turn).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, (src, extra, _) in [job for table in JOB_TABLES for job in table.items()]:
+    for out, (src, extra, _) in [job for table in ALL_JOB_TABLES for job in table.items()]:
         if not force and not is_stale(out):
             continue
         cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]

@@ -46,7 +46,14 @@ WAV header then say; default empty = off) and `correlate` (FILE.npy[:threshold[:
 [Q][K]; every lag of every block gets its normalised correlation against each template, and the lags at which it peaks at or
 above threshold (default 0.5) within guard lags on either side (default K) are listed; handed off as d['corrEvents'] (block is
 the running block index of the run) and d['corrTotal']; default empty = off), `correlateSave` (an .npz of the events, toa =
-block, fractional position and seconds inside the block, and the parameters).
+block, fractional position and seconds inside the block, and the parameters), `pulses`
+([rel:]ON_DB:OFF_DB[:W[:minLen[:events=N]]], zeroSpan only, not with `zoom` or `channels`, allowed beside `correlate`: a
+time-domain pulse detector over every frame's raw block -- the power summed over W samples (default 16) is compared with a trigger
+level that has hysteresis, ON_DB to start a pulse and OFF_DB <= ON_DB to end it, in dB relative to full scale as 10 log10 of the
+mean power, or with rel: in dB above the median envelope of the first block; runs shorter than minLen (default 1) are dropped;
+handed off as d['pulseEvents'] (block is the running block index of the run), d['pulseTotal'] and d['pulseActive']; default
+empty = off) and `pulsesSave` (an .npz of the records, both totals, the parameters, and every pulse's toa_s, width_s, mean_dbfs,
+peak_dbfs and freq_hz).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -81,6 +88,8 @@ from . import resamp as _resamp
 from .resamp import Resampler, resample_taps, rate_ratio
 from . import corr as _corr
 from .corr import Correlator, refine
+from . import pulse as _pulse
+from .pulse import PulseDetector
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -115,6 +124,7 @@ _KEYS = {
     "DEMOD": ("demod", str), "DEMODSAVE": ("demodSave", str),
     "CHANNELS": ("channels", str), "CHANNELSSAVE": ("channelsSave", str), "AUDIORATE": ("audioRate", str),
     "CORRELATE": ("correlate", str), "CORRELATESAVE": ("correlateSave", str),
+    "PULSES": ("pulses", str), "PULSESSAVE": ("pulsesSave", str),
 }
 
 
@@ -132,7 +142,7 @@ def defaults():
         "source": "rtlsdr", "device": 0, "iqFormat": "c64", "frameBatch": 1, "pfbTaps": 0, "pfbSpectra": 0, "cmd.stop": False,
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
         "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
-        "audioRate": "", "correlate": "", "correlateSave": "",
+        "audioRate": "", "correlate": "", "correlateSave": "", "pulses": "", "pulsesSave": "",
     }
 
 
@@ -221,6 +231,7 @@ def handle_args(d, argv=None):
     _handle_demod(d)
     _handle_resample(d)
     _handle_correlate(d)
+    _handle_pulses(d)
     return d
 
 
@@ -533,6 +544,60 @@ def _handle_correlate(d):
         prg_quit(d, "ERROR:handle_args: correlate [{}]: a block of fullSize [{}] samples is shorter than the template of [{}]".format(
             text, d["fullSize"], k))
     d["corr.spec"] = spec
+
+
+PULSE_RULE = ("pulses wants [rel:]ON_DB:OFF_DB[:W[:minLen[:events=N]]] with finite levels OFF_DB <= ON_DB in dB relative to full "
+              "scale (10 log10 of the mean power, at most %.2f; with rel: in dB above the median envelope of the first block), an "
+              "integer 1 <= W <= %d samples (default 16), 1 <= minLen <= %d samples (default 1) and 1 <= N <= %d events (default "
+              "1024)" % (10 * np.log10(4.0), _pulse.MAX_W, _pulse.MAX_MIN_LEN, _pulse.MAX_CAPACITY))
+
+
+def _handle_pulses(d):
+    """pulses [rel:]ON_DB:OFF_DB[:W[:minLen[:events=N]]] (additive, zeroSpan only): d['pulse.spec'] = dict(rel, on_db, off_db,
+    W, min_len, capacity), or None when the key is off."""
+    d["pulse.spec"] = None
+    text = d["pulses"]
+    if not text:
+        if d["pulsesSave"]:
+            print("WARN:handle_args: pulsesSave [{}] is ignored without pulses".format(d["pulsesSave"]))
+        return
+    spec = dict(rel=False, on_db=0.0, off_db=0.0, W=16, min_len=1, capacity=1024)
+    try:
+        parts = text.split(":")
+        if parts[0].lower() == "rel":
+            spec["rel"] = True
+            parts = parts[1:]
+        if not 2 <= len(parts) <= 5:
+            raise ValueError(text)
+        spec["on_db"], spec["off_db"] = float(parts[0]), float(parts[1])
+        if len(parts) > 2:
+            spec["W"] = int(parts[2])
+        if len(parts) > 3:
+            spec["min_len"] = int(parts[3])
+        if len(parts) > 4:
+            name, eq, value = parts[4].partition("=")
+            if not eq or name.lower() != "events":
+                raise ValueError(text)
+            spec["capacity"] = int(value)
+        if not (np.isfinite(spec["on_db"]) and np.isfinite(spec["off_db"]) and spec["off_db"] <= spec["on_db"]
+                and 1 <= spec["W"] <= _pulse.MAX_W and 1 <= spec["min_len"] <= _pulse.MAX_MIN_LEN
+                and 1 <= spec["capacity"] <= _pulse.MAX_CAPACITY):
+            raise ValueError(text)
+        if not spec["rel"]:                      # the absolute levels are the library's: 0 < off <= on <= 4, thr_off >= 1
+            on, off = _pulse.db_to_power(spec["on_db"]), _pulse.db_to_power(spec["off_db"])
+            if not (0 < off <= on <= 4 and round(off * _pulse.POWER_UNIT * spec["W"]) >= 1):
+                raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: pulses [{}]: {}".format(text, PULSE_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: pulses [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: pulses [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["zoom"] or d["channels"]:
+        prg_quit(d, "ERROR:handle_args: pulses [{}] reads the raw blocks: detecting pulses behind zoom or channels is out of scope, "
+                    "drop [{}]".format(text, "zoom" if d["zoom"] else "channels"))
+    d["pulse.spec"] = spec
 
 
 DEMOD_PCM_SCALE = 32767.0                    # int16 per unit of the filtered detector: AM full scale 1, FM and PM one cycle
@@ -1157,9 +1222,12 @@ def zero_span(d):
     bank = _ChanFeed(d, cspec, batch) if cspec is not None else None
     kspec = d.get("corr.spec") if sdr_curscan is _gpu_curscan else None
     corr = _CorrFeed(d, kspec, batch) if kspec is not None else None
+    pspec = d.get("pulse.spec") if sdr_curscan is _gpu_curscan else None
+    puls = _PulseFeed(d, pspec, batch) if pspec is not None else None
     try:
-        if batch > 1 or dens is not None or trig is not None or front is not None or det is not None or corr is not None:    # density, mask, zoom, detect and correlate run the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank, corr)
+        if (batch > 1 or dens is not None or trig is not None or front is not None or det is not None or corr is not None
+                or puls is not None):    # density, mask, zoom, detect, correlate and pulses run the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank, corr, puls)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
@@ -1174,7 +1242,11 @@ def zero_span(d):
             bank.handoff(d)
         if corr is not None:
             corr.handoff(d)
+        if puls is not None:
+            puls.handoff(d)
     finally:
+        if puls is not None:
+            puls.close()
         if corr is not None:
             corr.close()
         if audio is not None:
@@ -1341,6 +1413,69 @@ class _CorrFeed:
         self.corr.close()
 
 
+class _PulseFeed:
+    """The pulses key's state over a run: the PulseDetector, whose block form runs over every batch's raw blocks in their
+    iqFormat, read from the page-locked batch buffer; block numbers are frame numbers of the run.  With rel: the levels are set
+    from the median envelope of the run's first block before any block is searched."""
+
+    def __init__(self, d, spec, batch):
+        self.spec, self.full, self.rate = spec, d["fullSize"], d["samplingRate"]
+        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
+        on, off = (1.0, 1.0) if spec["rel"] else (_pulse.db_to_power(spec["on_db"]), _pulse.db_to_power(spec["off_db"]))
+        self.det = PulseDetector(W=spec["W"], on_power=on, off_power=off, min_len=spec["min_len"], capacity=spec["capacity"],
+                                 max_in=batch * self.full, fmt=fmt, device=d["device"])
+        self.floor = None                            # rel: the median of S / W over the first block, in units of 2^-30
+        self.blocks_done, self.stored, self.parts = 0, 0, []
+
+    def _set_relative_levels(self, blocks):
+        """One dense pass over the run's first block; its records are dropped and the levels replaced."""
+        env = _engine.PinnedBuffer((self.full,), np.int64)
+        try:
+            self.det.blocks_dev(blocks, 1, self.full, env=env.array)
+            self.det.synchronize()
+            self.floor = float(np.median(env.array)) / self.spec["W"]
+        finally:
+            env.close()
+        self.det.clear_events()
+        base = self.floor / _pulse.POWER_UNIT
+        self.det.set_params(base * 10.0 ** (self.spec["on_db"] / 10.0), base * 10.0 ** (self.spec["off_db"] / 10.0))
+
+    def feed(self, blocks, got):
+        """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
+        if self.spec["rel"] and self.floor is None:
+            self._set_relative_levels(blocks)
+        self.det.blocks_dev(blocks, got, self.full)
+        if self.stored < self.det.capacity:
+            ev = self.det.events()[0]                # synchronises: the buffer is free for the next batch
+            new = ev[self.stored:]
+            new["block"] += self.blocks_done
+            self.parts.append(new)
+            self.stored = len(ev)
+        else:
+            self.det.synchronize()
+        self.blocks_done += got
+
+    def handoff(self, d):
+        """The hand-off arrays, the INFO line, pulsesSave."""
+        _, total, active = self.det.events()
+        ev = np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=_pulse.EVENT_DTYPE)
+        d["pulseEvents"], d["pulseTotal"], d["pulseActive"] = ev, total, active
+        thr_on, thr_off = self.det.thresholds()
+        print("INFO:zero_span: pulses blocks [{}], W [{}], thr_on [{}] thr_off [{}], pulses stored [{}] / total [{}], active samples [{}]".format(
+            self.blocks_done, self.det.W, thr_on, thr_off, len(ev), total, active))
+        if d["pulsesSave"]:
+            s = self.spec
+            with open(d["pulsesSave"], "wb") as f:
+                np.savez(f, events=ev, pulses_total=np.int64(total), active_total=np.int64(active), rel=np.bool_(s["rel"]),
+                         on_db=np.float64(s["on_db"]), off_db=np.float64(s["off_db"]), W=np.int32(s["W"]),
+                         min_len=np.int32(s["min_len"]), capacity=np.int32(s["capacity"]), thr_on=np.int64(thr_on),
+                         thr_off=np.int64(thr_off), sampling_rate=np.float64(self.rate), block_len=np.int64(self.full),
+                         **_pulse.describe(ev, s["W"], self.rate, self.full))
+
+    def close(self):
+        self.det.close()
+
+
 class _DemodFeed:
     """The demod key's state over a run: the Demodulator behind the down-converter, fed every batch's zoomed blocks in device
     memory; each block is demodulated on its own and the blocks abut in the audio."""
@@ -1466,7 +1601,8 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None, bank=None, corr=None):
+def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None, bank=None, corr=None,
+                       puls=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
@@ -1480,7 +1616,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
     (kdm_blocks_dev) and the batch's int16 audio is fetched with kdm_read_out.  With channels in place of zoom every block is
     the channelizer's block length, kch_blocks_dev leaves [got][M][fullSize] complex64 in its buffer, and the engine and the
     demodulator read the picked channel of every block at a stride of M x fullSize values.  With correlate (never together with
-    a front end) the correlator's block form reads the batch's raw blocks from the same page-locked buffer (kcr_blocks_dev)."""
+    a front end) the correlator's block form reads the batch's raw blocks from the same page-locked buffer (kcr_blocks_dev), and
+    with pulses the pulse detector's block form does (kpl_blocks_dev)."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
     full = zoom["block_len"] if zoom is not None else bank.spec["block_len"] if bank is not None else d["fullSize"]
     dtype, per = raw_dtype(u8)
@@ -1539,6 +1676,8 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
                     det.feed(db)
             if got and corr is not None:
                 corr.feed(blocks, got)
+            if got and puls is not None:
+                puls.feed(blocks, got)
             done += got
             if got < k:
                 prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)
