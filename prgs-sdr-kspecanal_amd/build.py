@@ -1,4 +1,4 @@
-"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of ALL_TABLES below).  In-tree, no
+"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of EVERY_TABLES below).  In-tree, no
 JIT cache: every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's
 sources with -DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
 import os
@@ -34,7 +34,12 @@ TABLES = [PRODUCTS, MORE_PRODUCTS, LATER_PRODUCTS]      # the tables up to the c
 PULSE_PRODUCTS = {
     "libksa_pulse.so": ("csrc_pulse", "kpl_api.hip", "ksa_pulse.h", []),
 }
-ALL_TABLES = TABLES + [PULSE_PRODUCTS]                  # every product of every table is built, in this order
+ALL_TABLES = TABLES + [PULSE_PRODUCTS]                  # the tables up to the pulse detector, in this order
+# the emission tracker, in a table of its own again: every table and list above stays as it was
+TRACK_PRODUCTS = {
+    "libksa_track.so": ("csrc_track", "ktr_api.hip", "ksa_track.h", []),
+}
+EVERY_TABLES = ALL_TABLES + [TRACK_PRODUCTS]            # every product of every table is built, in this order
 OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 
@@ -47,7 +52,7 @@ def _files(subdir):
 def _sources(product):
     """Every file the product depends on: its directory, its header and, for a companion library, csrc_shared/ (which csrc/
     does not include)."""
-    subdir, _, header, _ = next(table[product] for table in ALL_TABLES if product in table)
+    subdir, _, header, _ = next(table[product] for table in EVERY_TABLES if product in table)
     shared = _files("csrc_shared") if subdir != "csrc" else []
     return _files(subdir) + shared + [os.path.join(HERE, "..", "include", header)]
 
@@ -68,20 +73,22 @@ LATER_JOBS = _jobs(LATER_PRODUCTS)
 JOB_TABLES = [JOBS, MORE_JOBS, LATER_JOBS]              # one per entry of TABLES
 PULSE_JOBS = _jobs(PULSE_PRODUCTS)
 ALL_JOB_TABLES = JOB_TABLES + [PULSE_JOBS]              # one per entry of ALL_TABLES
+TRACK_JOBS = _jobs(TRACK_PRODUCTS)
+EVERY_JOB_TABLES = ALL_JOB_TABLES + [TRACK_JOBS]        # one per entry of EVERY_TABLES
 
 
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in ALL_JOB_TABLES if out in jobs)[2]())
+    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in EVERY_JOB_TABLES if out in jobs)[2]())
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the libraries side by side, the tables of ALL_JOB_TABLES in turn).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the libraries side by side, the tables of EVERY_JOB_TABLES in turn).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, (src, extra, _) in [job for table in ALL_JOB_TABLES for job in table.items()]:
+    for out, (src, extra, _) in [job for table in EVERY_JOB_TABLES for job in table.items()]:
         if not force and not is_stale(out):
             continue
         cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]

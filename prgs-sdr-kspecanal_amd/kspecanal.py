@@ -52,8 +52,13 @@ time-domain pulse detector over every frame's raw block -- the power summed over
 level that has hysteresis, ON_DB to start a pulse and OFF_DB <= ON_DB to end it, in dB relative to full scale as 10 log10 of the
 mean power, or with rel: in dB above the median envelope of the first block; runs shorter than minLen (default 1) are dropped;
 handed off as d['pulseEvents'] (block is the running block index of the run), d['pulseTotal'] and d['pulseActive']; default
-empty = off) and `pulsesSave` (an .npz of the records, both totals, the parameters, and every pulse's toa_s, width_s, mean_dbfs,
-peak_dbfs and freq_hz).
+empty = off), `pulsesSave` (an .npz of the records, both totals, the parameters, and every pulse's toa_s, width_s, mean_dbfs,
+peak_dbfs and freq_hz), `track` (GAP:SLOP[:minRows=R][:minSpans=S][:events=E], zeroSpan only, needs `detect`: at the end of the
+run the detector's emissions are linked on the GPU into time-frequency tracks -- emissions at most GAP missing frames apart whose
+bins overlap or miss each other by at most SLOP bins are one track, tracks over fewer than R frames or of fewer than S emissions
+are dropped; handed off as d['trackTracks'], d['trackTotal'], d['trackComponents'] and d['trackLabels'], the track of every
+stored emission; default empty = off) and `trackSave` (an .npz of the records, both totals, the labels, the parameters, and
+every track's t_start_s, duration_s, center_hz, width_hz and drift_hz_per_s).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -90,6 +95,8 @@ from . import corr as _corr
 from .corr import Correlator, refine
 from . import pulse as _pulse
 from .pulse import PulseDetector
+from . import track as _track
+from .track import EmissionTracker, track_times_freqs
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -125,6 +132,7 @@ _KEYS = {
     "CHANNELS": ("channels", str), "CHANNELSSAVE": ("channelsSave", str), "AUDIORATE": ("audioRate", str),
     "CORRELATE": ("correlate", str), "CORRELATESAVE": ("correlateSave", str),
     "PULSES": ("pulses", str), "PULSESSAVE": ("pulsesSave", str),
+    "TRACK": ("track", str), "TRACKSAVE": ("trackSave", str),
 }
 
 
@@ -143,6 +151,7 @@ def defaults():
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
         "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
         "audioRate": "", "correlate": "", "correlateSave": "", "pulses": "", "pulsesSave": "",
+        "track": "", "trackSave": "",
     }
 
 
@@ -232,6 +241,7 @@ def handle_args(d, argv=None):
     _handle_resample(d)
     _handle_correlate(d)
     _handle_pulses(d)
+    _handle_track(d)
     return d
 
 
@@ -480,6 +490,50 @@ def _handle_detect(d):
     if d["bUsePSD"]:
         prg_quit(d, "ERROR:handle_args: detect [{}] needs bUsePSD false: it reads the engine's own dB rows".format(text))
     d["detect.spec"] = spec
+
+
+TRACK_RULE = ("track wants GAP:SLOP with integers 0 <= GAP <= %d missing frames and 0 <= SLOP <= fftSize bins, optionally followed "
+              "by :minRows=R (>= 1), :minSpans=S (>= 1) and :events=E (1..%d, default 4096), each at most once" % (
+                  _track.MAX_ROW_GAP, _track.MAX_CAPACITY))
+
+
+def _handle_track(d):
+    """track GAP:SLOP[:minRows=R][:minSpans=S][:events=E] (additive, zeroSpan only, needs detect): d['track.spec'] =
+    dict(row_gap, bin_slop, min_rows, min_spans, capacity), or None when the key is off."""
+    d["track.spec"] = None
+    text = d["track"]
+    if not text:
+        if d["trackSave"]:
+            print("WARN:handle_args: trackSave [{}] is ignored without track".format(d["trackSave"]))
+        return
+    spec = dict(row_gap=0, bin_slop=0, min_rows=1, min_spans=1, capacity=4096)
+    try:
+        parts = text.split(":")
+        if len(parts) < 2:
+            raise ValueError(text)
+        spec["row_gap"], spec["bin_slop"] = int(parts[0]), int(parts[1])
+        seen = set()
+        for part in parts[2:]:                       # the optional suffixes, in any order, each at most once
+            name, eq, value = part.partition("=")
+            key = {"minrows": "min_rows", "minspans": "min_spans", "events": "capacity"}.get(name.lower())
+            if not eq or key is None or key in seen:
+                raise ValueError(text)
+            seen.add(key)
+            spec[key] = int(value)
+        if not (0 <= spec["row_gap"] <= _track.MAX_ROW_GAP and 0 <= spec["bin_slop"] <= d["fftSize"]
+                and 1 <= spec["min_rows"] < 2 ** 31 and 1 <= spec["min_spans"] < 2 ** 31
+                and 1 <= spec["capacity"] <= _track.MAX_CAPACITY):
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: track [{}]: {}".format(text, TRACK_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: track [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: track [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["detect.spec"] is None:
+        prg_quit(d, "ERROR:handle_args: track [{}] links the emissions of detect: give [detect T:G:THR] as well".format(text))
+    d["track.spec"] = spec
 
 
 CORR_RULE = ("correlate wants FILE.npy[:threshold[:guard[:events=N]]] with a finite 0 < threshold <= 1 (default 0.5), an integer "
@@ -1236,6 +1290,8 @@ def zero_span(d):
             trig.handoff(d)
         if det is not None:
             det.handoff(d, freqs)
+            if d.get("track.spec") is not None:  # one row is one frame: fullSize samples at the rate the engine was fed
+                det.link(d, freqs, d["fullSize"] * (front["decim"] if front is not None else 1) / d["samplingRate"])
         if audio is not None:
             audio.handoff(d)
         if bank is not None:
@@ -1363,6 +1419,29 @@ class _DetectFeed:
                          train=np.int32(s["train"]), guard=np.int32(s["guard"]), threshold_db=np.float32(s["threshold"]),
                          mode=np.array(s["mode"]), min_width=np.int32(s["min_width"]), max_gap=np.int32(s["max_gap"]),
                          center_hz=center, width_hz=width)
+
+    def link(self, d, freqs, row_period_s):
+        """The track key: one link over the detector's whole buffer where it lies; the hand-off arrays, the INFO line,
+        trackSave."""
+        s = d["track.spec"]
+        trk = EmissionTracker(d["fftSize"], row_gap=s["row_gap"], bin_slop=s["bin_slop"], min_rows=s["min_rows"],
+                              min_spans=s["min_spans"], capacity=s["capacity"], max_spans=self.det.capacity, device=d["device"])
+        try:
+            trk.link_detector(self.det)
+            tr, total, comps = trk.tracks()
+            labels = trk.labels()
+        finally:
+            trk.close()
+        d["trackTracks"], d["trackTotal"], d["trackComponents"], d["trackLabels"] = tr, total, comps, labels
+        longest = int((tr["row_last"] - tr["row_first"] + 1).max()) if len(tr) else 0
+        print("INFO:zero_span: track emissions [{}], components [{}], tracks stored [{}] / total [{}], longest [{}] rows, open at the end [{}]".format(
+            len(labels), comps, len(tr), total, longest, int(np.count_nonzero(tr["flags"] & _track.FLAG_OPEN_END))))
+        if d["trackSave"]:
+            with open(d["trackSave"], "wb") as f:
+                np.savez(f, tracks=tr, tracks_total=np.int64(total), components_total=np.int64(comps), labels=labels,
+                         row_gap=np.int32(s["row_gap"]), bin_slop=np.int32(s["bin_slop"]), min_rows=np.int32(s["min_rows"]),
+                         min_spans=np.int32(s["min_spans"]), capacity=np.int32(s["capacity"]),
+                         row_period_s=np.float64(row_period_s), **track_times_freqs(tr, freqs, row_period_s))
 
     def close(self):
         self.det.close()
