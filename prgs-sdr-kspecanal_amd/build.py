@@ -1,4 +1,4 @@
-"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of EVERY_TABLES below).  In-tree, no
+"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of WHOLE_TABLES below).  In-tree, no
 JIT cache: every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's
 sources with -DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
 import os
@@ -39,7 +39,12 @@ ALL_TABLES = TABLES + [PULSE_PRODUCTS]                  # the tables up to the p
 TRACK_PRODUCTS = {
     "libksa_track.so": ("csrc_track", "ktr_api.hip", "ksa_track.h", []),
 }
-EVERY_TABLES = ALL_TABLES + [TRACK_PRODUCTS]            # every product of every table is built, in this order
+EVERY_TABLES = ALL_TABLES + [TRACK_PRODUCTS]            # the tables up to the tracker, in this order
+# the IQ corrector, in a table of its own once more: every table and list above stays as it was
+IQFIX_PRODUCTS = {
+    "libksa_iqfix.so": ("csrc_iqfix", "kqf_api.hip", "ksa_iqfix.h", []),
+}
+WHOLE_TABLES = EVERY_TABLES + [IQFIX_PRODUCTS]          # every product of every table is built, in this order
 OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 
@@ -52,7 +57,7 @@ def _files(subdir):
 def _sources(product):
     """Every file the product depends on: its directory, its header and, for a companion library, csrc_shared/ (which csrc/
     does not include)."""
-    subdir, _, header, _ = next(table[product] for table in EVERY_TABLES if product in table)
+    subdir, _, header, _ = next(table[product] for table in WHOLE_TABLES if product in table)
     shared = _files("csrc_shared") if subdir != "csrc" else []
     return _files(subdir) + shared + [os.path.join(HERE, "..", "include", header)]
 
@@ -75,20 +80,22 @@ PULSE_JOBS = _jobs(PULSE_PRODUCTS)
 ALL_JOB_TABLES = JOB_TABLES + [PULSE_JOBS]              # one per entry of ALL_TABLES
 TRACK_JOBS = _jobs(TRACK_PRODUCTS)
 EVERY_JOB_TABLES = ALL_JOB_TABLES + [TRACK_JOBS]        # one per entry of EVERY_TABLES
+IQFIX_JOBS = _jobs(IQFIX_PRODUCTS)
+WHOLE_JOB_TABLES = EVERY_JOB_TABLES + [IQFIX_JOBS]      # one per entry of WHOLE_TABLES
 
 
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in EVERY_JOB_TABLES if out in jobs)[2]())
+    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in WHOLE_JOB_TABLES if out in jobs)[2]())
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the libraries side by side, the tables of EVERY_JOB_TABLES in turn).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the libraries side by side, the tables of WHOLE_JOB_TABLES in turn).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, (src, extra, _) in [job for table in EVERY_JOB_TABLES for job in table.items()]:
+    for out, (src, extra, _) in [job for table in WHOLE_JOB_TABLES for job in table.items()]:
         if not force and not is_stale(out):
             continue
         cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]

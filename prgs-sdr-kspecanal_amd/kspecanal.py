@@ -58,7 +58,12 @@ run the detector's emissions are linked on the GPU into time-frequency tracks --
 bins overlap or miss each other by at most SLOP bins are one track, tracks over fewer than R frames or of fewer than S emissions
 are dropped; handed off as d['trackTracks'], d['trackTotal'], d['trackComponents'] and d['trackLabels'], the track of every
 stored emission; default empty = off) and `trackSave` (an .npz of the records, both totals, the labels, the parameters, and
-every track's t_start_s, duration_s, center_hz, width_hz and drift_hz_per_s).
+every track's t_start_s, duration_s, center_hz, width_hz and drift_hz_per_s), `iqfix` (MODE[:blocks=N][:track] with MODE
+dc|iq|dc+iq, zeroSpan only, not with `channels`, `correlate`, `pulses` or bUsePSD true: a blind DC-offset and IQ-imbalance
+corrector in front of everything else -- the sums of the first N blocks of the first batch (default all of it) are solved into a
+correction that every block of the run then gets before the engine (or `zoom`) sees it; with track every batch is corrected
+with the coefficients solved from the batch before it; handed off as d['iqfix'], a dict of per-solve arrays; default empty =
+off) and `iqfixSave` (an .npz of those arrays: batch, dc_i, dc_q, c, d, flags, count, sums, gain_db and phase_deg per solve).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -97,6 +102,8 @@ from . import pulse as _pulse
 from .pulse import PulseDetector
 from . import track as _track
 from .track import EmissionTracker, track_times_freqs
+from . import iqfix as _iqfix
+from .iqfix import IqCorrector
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -133,6 +140,7 @@ _KEYS = {
     "CORRELATE": ("correlate", str), "CORRELATESAVE": ("correlateSave", str),
     "PULSES": ("pulses", str), "PULSESSAVE": ("pulsesSave", str),
     "TRACK": ("track", str), "TRACKSAVE": ("trackSave", str),
+    "IQFIX": ("iqfix", str.lower), "IQFIXSAVE": ("iqfixSave", str),
 }
 
 
@@ -151,7 +159,7 @@ def defaults():
         "density": "", "densitySave": "", "mask": "", "maskSave": "", "zoom": "",
         "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
         "audioRate": "", "correlate": "", "correlateSave": "", "pulses": "", "pulsesSave": "",
-        "track": "", "trackSave": "",
+        "track": "", "trackSave": "", "iqfix": "", "iqfixSave": "",
     }
 
 
@@ -242,6 +250,7 @@ def handle_args(d, argv=None):
     _handle_correlate(d)
     _handle_pulses(d)
     _handle_track(d)
+    _handle_iqfix(d)
     return d
 
 
@@ -652,6 +661,58 @@ def _handle_pulses(d):
         prg_quit(d, "ERROR:handle_args: pulses [{}] reads the raw blocks: detecting pulses behind zoom or channels is out of scope, "
                     "drop [{}]".format(text, "zoom" if d["zoom"] else "channels"))
     d["pulse.spec"] = spec
+
+
+IQFIX_RULE = ("iqfix wants MODE[:blocks=N][:track] with MODE dc|iq|dc+iq, an integer 1 <= N <= frameBatch blocks of the first batch "
+              "that are measured (default: all of it), or track: every batch is measured and corrects the next; blocks= and track "
+              "exclude each other")
+
+
+def _handle_iqfix(d):
+    """iqfix MODE[:blocks=N][:track] (additive, zeroSpan only): d['iqfix.spec'] = dict(mode, blocks, track), or None when the
+    key is off; mode is the library's bits and blocks is None for all of the first batch."""
+    d["iqfix.spec"] = None
+    text = d["iqfix"]
+    if not text:
+        if d["iqfixSave"]:
+            print("WARN:handle_args: iqfixSave [{}] is ignored without iqfix".format(d["iqfixSave"]))
+        return
+    spec = dict(mode=0, blocks=None, track=False)
+    try:
+        parts = text.split(":")
+        if parts[0] not in _iqfix.MODES:
+            raise ValueError(text)
+        spec["mode"] = _iqfix.MODES[parts[0]]
+        for part in parts[1:]:
+            name, eq, value = part.partition("=")
+            if name == "track" and not eq and not spec["track"]:
+                spec["track"] = True
+            elif name == "blocks" and eq and spec["blocks"] is None:
+                spec["blocks"] = int(value)
+                if not 1 <= spec["blocks"] <= d["frameBatch"]:
+                    raise ValueError(text)
+            else:
+                raise ValueError(text)
+        if spec["track"] and spec["blocks"] is not None:
+            raise ValueError(text)
+    except ValueError:
+        prg_quit(d, "ERROR:handle_args: iqfix [{}]: {}".format(text, IQFIX_RULE))
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: iqfix [{}] is ignored when playing saved spectra".format(text))
+        return
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: iqfix [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
+    if d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: iqfix [{}] needs bUsePSD false: the PSD diagnostic reads the raw block".format(text))
+    for other in ("channels", "correlate", "pulses"):
+        if d[other]:
+            prg_quit(d, "ERROR:handle_args: iqfix [{}] corrects the blocks the engine and zoom read: {} [{}] reads the raw blocks, "
+                        "drop either".format(text, other, d[other]))
+    block_len = d["zoom.spec"]["block_len"] if d["zoom.spec"] is not None else d["fullSize"]
+    if d["frameBatch"] * block_len > _iqfix.MAX_IN:
+        prg_quit(d, "ERROR:handle_args: iqfix [{}]: frameBatch [{}] x [{}] samples per block exceed the corrector's [{}] per call".format(
+            text, d["frameBatch"], block_len, _iqfix.MAX_IN))
+    d["iqfix.spec"] = spec
 
 
 DEMOD_PCM_SCALE = 32767.0                    # int16 per unit of the filtered detector: AM full scale 1, FM and PM one cycle
@@ -1278,10 +1339,12 @@ def zero_span(d):
     corr = _CorrFeed(d, kspec, batch) if kspec is not None else None
     pspec = d.get("pulse.spec") if sdr_curscan is _gpu_curscan else None
     puls = _PulseFeed(d, pspec, batch) if pspec is not None else None
+    qspec = d.get("iqfix.spec") if sdr_curscan is _gpu_curscan else None
+    fix = _IqFeed(d, qspec, batch, zoom["block_len"] if zoom is not None else d["fullSize"]) if qspec is not None else None
     try:
         if (batch > 1 or dens is not None or trig is not None or front is not None or det is not None or corr is not None
-                or puls is not None):    # density, mask, zoom, detect, correlate and pulses run the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank, corr, puls)
+                or puls is not None or fix is not None):    # density, mask, zoom, detect, correlate, pulses and iqfix run the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank, corr, puls, fix=fix)
         else:
             _zero_span_frames(d, eng, freqs)
         if dens is not None:
@@ -1300,7 +1363,11 @@ def zero_span(d):
             corr.handoff(d)
         if puls is not None:
             puls.handoff(d)
+        if fix is not None:
+            fix.handoff(d)
     finally:
+        if fix is not None:
+            fix.close()
         if puls is not None:
             puls.close()
         if corr is not None:
@@ -1555,6 +1622,65 @@ class _PulseFeed:
         self.det.close()
 
 
+class _IqFeed:
+    """The iqfix key's state over a run: the IqCorrector in front of everything else.  It reads every batch's raw blocks in
+    their iqFormat from the page-locked batch buffer and leaves [got][block_len] complex64 in its own buffer.  Without track
+    the first batch's first `blocks` blocks are measured and solved once, before anything runs; with track every batch is
+    measured in the pass that corrects it, and what it solves to corrects the next one."""
+
+    def __init__(self, d, spec, batch, block_len):
+        self.spec, self.full = spec, block_len
+        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
+        self.fix = IqCorrector(fmt=fmt, max_in=batch * block_len, device=d["device"])
+        self.batches, self.solves = 0, []
+
+    @property
+    def out_ptr(self):
+        return self.fix.out_ptr
+
+    def _solve(self):
+        sums = self.fix.read_stats()
+        sol = self.fix.solve(self.spec["mode"])
+        self.solves.append((self.batches, sol, sums))
+
+    def run(self, blocks, got):
+        """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
+        if self.spec["track"]:
+            self.fix.blocks_dev(blocks, got, self.full, accumulate=True)
+            self._solve()                            # synchronises; the new coefficients serve the next batch
+            self.fix.clear_stats()
+        else:
+            if not self.solves:
+                self.fix.accumulate_dev(blocks, min(self.spec["blocks"] or got, got), self.full)
+                self._solve()
+            self.fix.blocks_dev(blocks, got, self.full)
+        self.batches += 1
+
+    def handoff(self, d):
+        """The hand-off dict, the INFO line, iqfixSave."""
+        sol = [s for _, s, _ in self.solves]
+        derived = [_iqfix.imbalance_of(s["c"], s["d"]) for s in sol]
+        out = {"batch": np.array([b for b, _, _ in self.solves], dtype=np.int64),
+               "sums": np.array([m for _, _, m in self.solves], dtype=np.int64).reshape(-1, 6),
+               "flags": np.array([s["flags"] for s in sol], dtype=np.int32),
+               "count": np.array([s["count"] for s in sol], dtype=np.int64),
+               "gain_db": np.array([g for g, _ in derived], dtype=np.float64),
+               "phase_deg": np.array([p for _, p in derived], dtype=np.float64)}
+        for k in ("dc_i", "dc_q", "c", "d"):
+            out[k] = np.array([s[k] for s in sol], dtype=np.float32)
+        d["iqfix"] = out
+        last = sol[-1] if sol else self.fix.get_coeffs()
+        print("INFO:zero_span: iqfix batches [{}], solves [{}], last dc [{}] [{}] c [{}] d [{}] flags [{}]".format(
+            self.batches, len(sol), last["dc_i"], last["dc_q"], last["c"], last["d"], last["flags"]))
+        if d["iqfixSave"]:
+            with open(d["iqfixSave"], "wb") as f:
+                np.savez(f, mode=np.int32(self.spec["mode"]), track=np.bool_(self.spec["track"]),
+                         blocks=np.int64(self.spec["blocks"] or 0), block_len=np.int64(self.full), **out)
+
+    def close(self):
+        self.fix.close()
+
+
 class _DemodFeed:
     """The demod key's state over a run: the Demodulator behind the down-converter, fed every batch's zoomed blocks in device
     memory; each block is demodulated on its own and the blocks abut in the audio."""
@@ -1681,7 +1807,7 @@ def _zero_span_frames(d, eng, freqs):
 
 
 def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None, bank=None, corr=None,
-                       puls=None):
+                       puls=None, fix=None):
     """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
     (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
     line and the plot refresh come once per batch.  prgLoopCnt still counts
@@ -1696,13 +1822,15 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
     the channelizer's block length, kch_blocks_dev leaves [got][M][fullSize] complex64 in its buffer, and the engine and the
     demodulator read the picked channel of every block at a stride of M x fullSize values.  With correlate (never together with
     a front end) the correlator's block form reads the batch's raw blocks from the same page-locked buffer (kcr_blocks_dev), and
-    with pulses the pulse detector's block form does (kpl_blocks_dev)."""
+    with pulses the pulse detector's block form does (kpl_blocks_dev).  With iqfix the corrector runs first: it reads the raw
+    batch from the page-locked buffer (kqf_blocks_dev) and leaves [got][block length] complex64 in its own buffer, which the
+    down-converter (then made for complex64) or the engine (ksa_frames_dev) reads instead of the raw batch."""
     u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
     full = zoom["block_len"] if zoom is not None else bank.spec["block_len"] if bank is not None else d["fullSize"]
     dtype, per = raw_dtype(u8)
     ddc = None
     if zoom is not None:
-        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[u8]
+        fmt = FMT_C64 if fix is not None else {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[u8]
         ddc = DownConverter(fmt, zoom["decim"], ddc_lowpass(zoom["decim"], zoom["taps_per_phase"]), freq=zoom["offset"],
                             sampling_rate=d["samplingRate"], max_in=batch * full, device=d["device"])
     stage = _engine.PinnedBuffer((batch, per * full), dtype)
@@ -1726,12 +1854,16 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
                         got += 1
                 except EOFError:
                     pass
-            if got and (ddc is not None or bank is not None):
+            if got and fix is not None:
+                fix.run(blocks, got)                                         # [got][full] complex64 in its own buffer
+            if got and (ddc is not None or bank is not None or fix is not None):
                 if ddc is not None:
-                    ddc.blocks_dev(blocks, got, full)                        # [got][fullSize] complex64 in its own buffer
+                    ddc.blocks_dev(blocks if fix is None else fix.out_ptr, got, full)   # [got][fullSize] complex64 in its own buffer
                     src, stride = ddc.out_ptr, None
-                else:
+                elif bank is not None:
                     src, stride = bank.run(blocks, got)                      # one channel of [got][M][fullSize]
+                else:
+                    src, stride = fix.out_ptr, None
                 db = eng._pinned_out("db", (got, d["fftSize"])) if dens is not None or trig is not None or det is not None else None
                 eng.frames_dev(src, FMT_C64, got, cur_db=db, frame_stride=stride)
                 eng.synchronize()
