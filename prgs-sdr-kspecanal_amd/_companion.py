@@ -1,13 +1,39 @@
-"""What the bindings of the six companion libraries (density, mask, ddc, detect, demod, chan) share: loading a library with its
-ABI check and signatures, and the lifetime, stream and kernel_info methods of the class over it.  _lib.py binds libksa.so on
-its own (it loads eagerly); there is no fallback here either: a missing library raises."""
+"""What the bindings of the companion libraries share: loading a library with its ABI check and signatures, the sample formats
+of the ones that take raw IQ, and the create, lifetime, stream and kernel_info methods of the class over it.  _lib.py binds
+libksa.so on its own (it loads eagerly); there is no fallback here either: a missing library raises."""
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import _lib
-from ._lib import KsaError
+from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+FORMATS = {"c64": FMT_C64, "u8": FMT_U8, "s8": FMT_S8, "s16": FMT_S16}
+SAMPLE_DTYPES = {FMT_C64: np.dtype(np.complex64), FMT_U8: np.dtype(np.uint8), FMT_S8: np.dtype(np.int8), FMT_S16: np.dtype(np.int16)}
+
+
+def format_of(fmt):
+    """The sample format as a number: a name of FORMATS in either case, or the number itself (the library checks its range)."""
+    if not isinstance(fmt, str):
+        return int(fmt)
+    if fmt.lower() not in FORMATS:
+        raise KsaError("unknown fmt [%s], expected one of %s" % (fmt, "|".join(FORMATS)))
+    return FORMATS[fmt.lower()]
+
+
+def host_iq(samples, fmt):
+    """(flat array, sample count) of host input that is not cast: complex64 [n], or for the integer formats [2n] I,Q of exactly
+    the format's dtype."""
+    a = np.ascontiguousarray(samples)
+    if fmt == FMT_C64:
+        a = np.ascontiguousarray(a, dtype=np.complex64).reshape(-1)
+        return a, a.size
+    want = SAMPLE_DTYPES[fmt]
+    if a.dtype != want or a.size % 2:
+        raise KsaError("process wants [2n] %s I,Q, got %s %s" % (want, a.dtype, a.shape))
+    return a.reshape(-1), a.size // 2
 
 
 class Binding:
@@ -49,11 +75,19 @@ class Binding:
 
 
 class Companion:
-    """Base of the six wrapper classes.  A subclass sets _binding and _info_fields (what k??_kernel_info reports after the
-    handle, in order) and its constructor leaves the library's handle in _h."""
+    """Base of the wrapper classes.  A subclass sets _binding and _info_fields (what k??_kernel_info reports after the
+    handle, in order) and its constructor ends in _create, which leaves the library's handle in _h."""
     _binding = None
     _info_fields = ()
     _h = None
+
+    def _create(self, *args, stream=None):
+        """k??_create(*args, &handle) through check, the handle into _h, then the stream if one was given."""
+        h = C.c_void_p()
+        self._binding.check(getattr(self._binding.lib(), self._binding.prefix + "create")(*args, C.byref(h)))
+        self._h = h
+        if stream is not None:
+            self.set_stream(stream)
 
     def _call(self, name, *args):
         self._binding.check(getattr(self._binding.lib(), self._binding.prefix + name)(self._h, *args))

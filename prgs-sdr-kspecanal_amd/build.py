@@ -1,4 +1,4 @@
-"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the tables of WHOLE_TABLES below).  In-tree, no
+"""Build the shared libraries for gfx950 with hipcc, one translation unit each (the PRODUCTS table below).  In-tree, no
 JIT cache: every .so sits next to this file so that it travels with the repository snapshot.  libksa_exp.so is libksa.so's
 sources with -DKSA_EXPERIMENTS, the only build that reads the KSA_* environment switches; the package never loads it."""
 import os
@@ -10,7 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-unused-value",
          "-shared", "-fPIC"]
 
-# product -> (source directory, the .hip that is compiled, public header under include/, extra flags)
+# product -> (source directory, the .hip that is compiled, public header under include/, extra flags); built in this order.
+# The next companion library is one more row.
 PRODUCTS = {
     "libksa.so": ("csrc", "ksa_api.hip", "ksa.h", []),
     "libksa_exp.so": ("csrc", "ksa_api.hip", "ksa.h", ["-DKSA_EXPERIMENTS"]),
@@ -20,31 +21,12 @@ PRODUCTS = {
     "libksa_detect.so": ("csrc_detect", "kse_api.hip", "ksa_detect.h", []),
     "libksa_demod.so": ("csrc_demod", "kdm_api.hip", "ksa_demod.h", []),
     "libksa_chan.so": ("csrc_chan", "kch_api.hip", "ksa_chan.h", []),
-}
-# the companions that came after those eight, in a table of the same shape: same FLAGS, same dependency on csrc_shared/
-MORE_PRODUCTS = {
     "libksa_resamp.so": ("csrc_resamp", "krs_api.hip", "ksa_resamp.h", []),
-}
-# and the ones after the resampler; the next companion is one more entry here
-LATER_PRODUCTS = {
     "libksa_corr.so": ("csrc_corr", "kcr_api.hip", "ksa_corr.h", []),
-}
-TABLES = [PRODUCTS, MORE_PRODUCTS, LATER_PRODUCTS]      # the tables up to the correlator, in this order
-# the pulse detector, in a table of its own: the three above and TABLES stay as they were
-PULSE_PRODUCTS = {
     "libksa_pulse.so": ("csrc_pulse", "kpl_api.hip", "ksa_pulse.h", []),
-}
-ALL_TABLES = TABLES + [PULSE_PRODUCTS]                  # the tables up to the pulse detector, in this order
-# the emission tracker, in a table of its own again: every table and list above stays as it was
-TRACK_PRODUCTS = {
     "libksa_track.so": ("csrc_track", "ktr_api.hip", "ksa_track.h", []),
-}
-EVERY_TABLES = ALL_TABLES + [TRACK_PRODUCTS]            # the tables up to the tracker, in this order
-# the IQ corrector, in a table of its own once more: every table and list above stays as it was
-IQFIX_PRODUCTS = {
     "libksa_iqfix.so": ("csrc_iqfix", "kqf_api.hip", "ksa_iqfix.h", []),
 }
-WHOLE_TABLES = EVERY_TABLES + [IQFIX_PRODUCTS]          # every product of every table is built, in this order
 OUT = os.path.join(HERE, "libksa.so")
 OUT_EXP = os.path.join(HERE, "libksa_exp.so")
 
@@ -57,7 +39,7 @@ def _files(subdir):
 def _sources(product):
     """Every file the product depends on: its directory, its header and, for a companion library, csrc_shared/ (which csrc/
     does not include)."""
-    subdir, _, header, _ = next(table[product] for table in WHOLE_TABLES if product in table)
+    subdir, _, header, _ = PRODUCTS[product]
     shared = _files("csrc_shared") if subdir != "csrc" else []
     return _files(subdir) + shared + [os.path.join(HERE, "..", "include", header)]
 
@@ -73,29 +55,20 @@ def _jobs(table):
 
 
 JOBS = _jobs(PRODUCTS)
-MORE_JOBS = _jobs(MORE_PRODUCTS)
-LATER_JOBS = _jobs(LATER_PRODUCTS)
-JOB_TABLES = [JOBS, MORE_JOBS, LATER_JOBS]              # one per entry of TABLES
-PULSE_JOBS = _jobs(PULSE_PRODUCTS)
-ALL_JOB_TABLES = JOB_TABLES + [PULSE_JOBS]              # one per entry of ALL_TABLES
-TRACK_JOBS = _jobs(TRACK_PRODUCTS)
-EVERY_JOB_TABLES = ALL_JOB_TABLES + [TRACK_JOBS]        # one per entry of EVERY_TABLES
-IQFIX_JOBS = _jobs(IQFIX_PRODUCTS)
-WHOLE_JOB_TABLES = EVERY_JOB_TABLES + [IQFIX_JOBS]      # one per entry of WHOLE_TABLES
 
 
 def is_stale(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(s) > t for s in next(jobs[out] for jobs in WHOLE_JOB_TABLES if out in jobs)[2]())
+    return any(os.path.getmtime(s) > t for s in JOBS[out][2]())
 
 
 def build(force=False, verbose=False):
-    """Compile what is missing or older than its sources (the libraries side by side, the tables of WHOLE_JOB_TABLES in turn).  Returns the product's path."""
+    """Compile what is missing or older than its sources (the libraries side by side).  Returns the product's path."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     jobs = []
-    for out, (src, extra, _) in [job for table in WHOLE_JOB_TABLES for job in table.items()]:
+    for out, (src, extra, _) in JOBS.items():
         if not force and not is_stale(out):
             continue
         cmd = [hipcc] + FLAGS + extra + ["-o", out + ".tmp", src]

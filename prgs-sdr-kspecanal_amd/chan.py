@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._companion import Binding, Companion
+from ._companion import Binding, Companion, host_iq
 from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
 from .engine import DevArray, _ptr, window_table
 
@@ -86,16 +86,12 @@ class Channelizer(Companion):
             raise KsaError("Channelizer wants nchan * taps_per_branch taps, got %d taps for %d channels" % (self.ntaps, self.nchan))
         self.taps_per_branch = self.ntaps // self.nchan
         self.decim = max(self.nchan // max(self.oversample, 1), 1)
-        h = C.c_void_p()
-        check(lib().kch_create(self.device, self.fmt, u8_offset, u8_scale, self.nchan, self.oversample, self.taps_per_branch,
-                               _ptr(self.taps), self.max_in, C.byref(h)))
-        self._h = h
+        self._create(self.device, self.fmt, u8_offset, u8_scale, self.nchan, self.oversample, self.taps_per_branch,
+                     _ptr(self.taps), self.max_in, stream=stream)
         self.first = -(-(self.ntaps - 1) // self.decim)
         p, rows, stride, cap = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int64()
         check(lib().kch_out_dev(self._h, C.byref(p), C.byref(rows), C.byref(stride), C.byref(cap)))
         self._out, self.out_stride, self.out_capacity = p.value, stride.value, cap.value
-        if stream is not None:
-            self.set_stream(stream)
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):
@@ -113,16 +109,7 @@ class Channelizer(Companion):
     def process(self, samples):
         """The stream's next samples from host memory (complex64 [n], or [2n] uint8 / int8 / int16 I,Q); complex64
         [nchan][columns]; synchronises."""
-        a = np.ascontiguousarray(samples)
-        if self.fmt == FMT_C64:
-            a = np.ascontiguousarray(a, dtype=np.complex64).reshape(-1)
-            n_in = a.size
-        else:
-            want = {FMT_U8: np.uint8, FMT_S8: np.int8, FMT_S16: np.int16}[self.fmt]
-            if a.dtype != want or a.size % 2:
-                raise KsaError("process wants [2n] %s I,Q, got %s %s" % (np.dtype(want), a.dtype, a.shape))
-            a = a.reshape(-1)
-            n_in = a.size // 2
+        a, n_in = host_iq(samples, self.fmt)
         cols = self.out_count(n_in)
         out = np.empty((self.nchan, cols), dtype=np.complex64)
         n = C.c_int64()

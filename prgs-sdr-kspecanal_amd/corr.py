@@ -7,14 +7,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._companion import Binding, Companion
+from ._companion import FORMATS, SAMPLE_DTYPES, Binding, Companion, format_of
 from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
 from .engine import DevArray, _ptr
 
 ABI_VERSION = 1
 MAX_K, MAX_Q, MAX_TEMPLATE_VALUES, MAX_GUARD, MAX_CAPACITY, MAX_IN, MAX_POSITION = 4096, 8, 16384, 4096, 1 << 20, 2 ** 28 - 1, 2 ** 52
-FORMATS = {"c64": FMT_C64, "u8": FMT_U8, "s8": FMT_S8, "s16": FMT_S16}
-SAMPLE_DTYPES = {FMT_C64: np.dtype(np.complex64), FMT_U8: np.dtype(np.uint8), FMT_S8: np.dtype(np.int8), FMT_S16: np.dtype(np.int16)}
 
 _P = C.c_void_p
 _I32, _I64, _F = C.c_int32, C.c_int64, C.c_float
@@ -95,21 +93,15 @@ class Correlator(Companion):
 
     def __init__(self, templates, threshold=0.5, min_energy=0.0, guard=None, capacity=4096, max_in=1 << 20, fmt="c64",
                  u8_offset=127.5, u8_scale=127.5, device=0, stream=None):
-        if isinstance(fmt, str) and fmt.lower() not in FORMATS:
-            raise KsaError("unknown fmt [%s], expected one of %s" % (fmt, "|".join(FORMATS)))
-        self.fmt = FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
+        self.fmt = format_of(fmt)
         self.templates = _templates(templates)
         self.Q, self.K = (int(v) for v in self.templates.shape)
         self.guard = self.K if guard is None else int(guard)
         self.threshold, self.min_energy = float(threshold), float(min_energy)
         self.capacity, self.max_in, self.device = int(capacity), int(max_in), int(device)
         self.in_dtype = SAMPLE_DTYPES.get(self.fmt, np.dtype(np.complex64))
-        h = C.c_void_p()
-        check(lib().kcr_create(self.device, self.fmt, float(u8_offset), float(u8_scale), self.K, self.Q, _ptr(self.templates),
-                               self.threshold, self.min_energy, self.guard, self.capacity, self.max_in, C.byref(h)))
-        self._h = h
-        if stream is not None:
-            self.set_stream(stream)
+        self._create(self.device, self.fmt, float(u8_offset), float(u8_scale), self.K, self.Q, _ptr(self.templates),
+                     self.threshold, self.min_energy, self.guard, self.capacity, self.max_in, stream=stream)
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):

@@ -174,7 +174,7 @@ int kch_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
                int32_t taps_per_branch, const float* taps_host, int64_t max_in, kch_chan** out) {
   if (!out) return fail("null out pointer");
   *out = nullptr;
-  if (fmt < KCH_FMT_C64 || fmt > KCH_FMT_S16) return fail("unknown sample format %d", fmt);
+  if (check_iq_format(fmt)) return 1;
   if (nchan < KCH_MIN_CHAN || nchan > KCH_MAX_CHAN || (nchan & (nchan - 1)))
     return fail("nchan %d must be a power of two, %d..%d", nchan, KCH_MIN_CHAN, KCH_MAX_CHAN);
   if (oversample != 1 && oversample != 2 && oversample != 4) return fail("oversample %d must be 1, 2 or 4", oversample);
@@ -186,11 +186,8 @@ int kch_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
   if (max_in < 1 || max_in > KCH_MAX_IN) return fail("max_in %lld outside 1..%d", (long long)max_in, KCH_MAX_IN);
   const int T = nchan * taps_per_branch;
   if (int rc = check_taps(T, taps_host)) return rc;
-  if (fmt == KCH_FMT_U8) {
-    if (!std::isfinite(u8_scale) || u8_scale == 0.f) return fail("u8_scale %g must be finite and non-zero", (double)u8_scale);
-    if (!std::isfinite(u8_offset)) return fail("u8_offset %g must be finite", (double)u8_offset);
-  }
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_u8_scaling(fmt, u8_offset, u8_scale)) return 1;
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -263,7 +263,7 @@ int kcr_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
                float threshold, float min_energy, int32_t guard, int32_t capacity, int64_t max_in, kcr_corr** out) {
   if (!out) return fail("null out pointer");
   *out = nullptr;
-  if (fmt < KCR_FMT_C64 || fmt > KCR_FMT_S16) return fail("unknown sample format %d", fmt);
+  if (check_iq_format(fmt)) return 1;
   if (K < 1 || K > KCR_MAX_K) return fail("K %d outside 1..%d", K, KCR_MAX_K);
   if (Q < 1 || Q > KCR_MAX_Q) return fail("Q %d outside 1..%d", Q, KCR_MAX_Q);
   if (Q * K > KCR_MAX_TEMPLATE_VALUES) return fail("Q x K = %d template values exceed %d", Q * K, KCR_MAX_TEMPLATE_VALUES);
@@ -273,11 +273,8 @@ int kcr_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
   if (guard < 1 || guard > KCR_MAX_GUARD) return fail("guard %d outside 1..%d", guard, KCR_MAX_GUARD);
   if (capacity < 1 || capacity > KCR_MAX_CAPACITY) return fail("event capacity %d outside 1..%d", capacity, KCR_MAX_CAPACITY);
   if (max_in < 1 || max_in > KCR_MAX_IN) return fail("max_in %lld outside 1..%d", (long long)max_in, KCR_MAX_IN);
-  if (fmt == KCR_FMT_U8) {
-    if (!std::isfinite(u8_scale) || u8_scale == 0.f) return fail("u8_scale %g must be finite and non-zero", (double)u8_scale);
-    if (!std::isfinite(u8_offset)) return fail("u8_offset %g must be finite", (double)u8_offset);
-  }
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_u8_scaling(fmt, u8_offset, u8_scale)) return 1;
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -171,16 +171,13 @@ int kdc_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
                const float* taps_host, uint64_t phase_inc, int64_t max_in, kdc_ddc** out) {
   if (!out) return fail("null out pointer");
   *out = nullptr;
-  if (fmt < KDC_FMT_C64 || fmt > KDC_FMT_S16) return fail("unknown sample format %d", fmt);
+  if (check_iq_format(fmt)) return 1;
   if (decim < 1 || decim > KDC_MAX_DECIM) return fail("decim %d outside 1..%d", decim, KDC_MAX_DECIM);
   if (ntaps < 1 || ntaps > KDC_MAX_TAPS) return fail("ntaps %d outside 1..%d", ntaps, KDC_MAX_TAPS);
   if (max_in < 1 || max_in > KDC_MAX_IN) return fail("max_in %lld outside 1..%d", (long long)max_in, KDC_MAX_IN);
   if (int rc = check_taps(ntaps, taps_host)) return rc;
-  if (fmt == KDC_FMT_U8) {
-    if (!std::isfinite(u8_scale) || u8_scale == 0.f) return fail("u8_scale %g must be finite and non-zero", (double)u8_scale);
-    if (!std::isfinite(u8_offset)) return fail("u8_offset %g must be finite", (double)u8_offset);
-  }
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_u8_scaling(fmt, u8_offset, u8_scale)) return 1;
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -173,7 +173,7 @@ int kdm_create(int32_t device, int32_t mode, int32_t decim, int32_t ntaps, const
   if (int rc = check_taps(ntaps, taps_host)) return rc;
   if (out_fmt == KDM_OUT_S16 && !(std::isfinite(pcm_scale) && pcm_scale > 0.f))
     return fail("pcm_scale %g must be finite and > 0", (double)pcm_scale);
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

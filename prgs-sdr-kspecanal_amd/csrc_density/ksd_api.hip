@@ -105,7 +105,7 @@ int ksd_create(int32_t device, int32_t nbins, int32_t width, int32_t levels, flo
     return fail("levels / (hi_db - lo_db) = %d / (%g - %g) is not a finite positive float32", levels, hi_db, lo_db);
   const long long cells = (long long)(levels + 1) * width;
   if (cells > KSD_MAX_CELLS) return fail("(levels + 1) * width = %lld exceeds %d cells (1 GiB of counters)", cells, KSD_MAX_CELLS);
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -159,7 +159,7 @@ int kse_create(int32_t device, int32_t nbins, int32_t train, int32_t guard, floa
   Params par;
   if (int rc = check_params(nbins, train, guard, threshold_db, mode, min_width, max_gap, &par)) return rc;
   if (capacity < 1 || capacity > KSE_MAX_CAPACITY) return fail("emission capacity %d outside 1..%d", capacity, KSE_MAX_CAPACITY);
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -182,13 +182,10 @@ const char* kqf_last_error(void) { return g_err.c_str(); }
 int kqf_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int64_t max_in, kqf_corrector** out) {
   if (!out) return fail("null out pointer");
   *out = nullptr;
-  if (fmt < KQF_FMT_C64 || fmt > KQF_FMT_S16) return fail("unknown sample format %d", fmt);
+  if (check_iq_format(fmt)) return 1;
   if (max_in < 1 || max_in > KQF_MAX_IN) return fail("max_in %lld outside 1..%d", (long long)max_in, KQF_MAX_IN);
-  if (fmt == KQF_FMT_U8) {
-    if (!std::isfinite(u8_scale) || u8_scale == 0.f) return fail("u8_scale %g must be finite and non-zero", (double)u8_scale);
-    if (!std::isfinite(u8_offset)) return fail("u8_offset %g must be finite", (double)u8_offset);
-  }
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_u8_scaling(fmt, u8_offset, u8_scale)) return 1;
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -150,7 +150,7 @@ int ksm_create(int32_t device, int32_t nbins, const float* upper_host, const flo
   if (min_bins > nbins) return fail("min_bins %d exceeds the %d bins of a row", min_bins, nbins);
   if (capacity < 1 || capacity > KSM_MAX_CAPACITY) return fail("event capacity %d outside 1..%d", capacity, KSM_MAX_CAPACITY);
   if (int rc = check_lines(nbins, upper_host, lower_host)) return rc;
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -196,18 +196,15 @@ int kpl_create(int32_t device, int32_t fmt, float u8_offset, float u8_scale, int
                int32_t min_len, int32_t capacity, int64_t max_in, kpl_detector** out) {
   if (!out) return fail("null out pointer");
   *out = nullptr;
-  if (fmt < KPL_FMT_C64 || fmt > KPL_FMT_S16) return fail("unknown sample format %d", fmt);
+  if (check_iq_format(fmt)) return 1;
   if (W < 1 || W > KPL_MAX_W) return fail("W %d outside 1..%d", W, KPL_MAX_W);
   long long thr_on = 0, thr_off = 0;
   if (int rc = check_params(on_power, off_power, W, &thr_on, &thr_off)) return rc;
   if (min_len < 1 || min_len > KPL_MAX_MIN_LEN) return fail("min_len %d outside 1..%d", min_len, KPL_MAX_MIN_LEN);
   if (capacity < 1 || capacity > KPL_MAX_CAPACITY) return fail("pulse capacity %d outside 1..%d", capacity, KPL_MAX_CAPACITY);
   if (max_in < 1 || max_in > KPL_MAX_IN) return fail("max_in %lld outside 1..%d", (long long)max_in, KPL_MAX_IN);
-  if (fmt == KPL_FMT_U8) {
-    if (!std::isfinite(u8_scale) || u8_scale == 0.f) return fail("u8_scale %g must be finite and non-zero", (double)u8_scale);
-    if (!std::isfinite(u8_offset)) return fail("u8_offset %g must be finite", (double)u8_offset);
-  }
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_u8_scaling(fmt, u8_offset, u8_scale)) return 1;
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -194,7 +194,7 @@ int krs_create(int32_t device, int32_t type, int32_t L, int32_t M, int32_t taps_
   const int P = taps_per_phase;
   if (max_in < 1 || max_in > KRS_MAX_IN) return fail("max_in %lld outside 1..%d", (long long)max_in, KRS_MAX_IN);
   if (int rc = check_create(type, L, M, P, taps_host, out_fmt, pcm_scale)) return rc;
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

@@ -1,9 +1,9 @@
-// Host layer that the six companion libraries (density, mask, ddc, detect, demod, chan) share: the error string, the device
-// guard and the stream, device-count and buffer steps that every k??_api.hip used to carry as its own copy.
+// Host layer that the companion libraries share: the error string, the device guard, the create-time checks and the stream,
+// device-count and buffer steps that every k??_api.hip used to carry as its own copy.
 // csrc_shared/ is a sibling of csrc/ and not inside it, because the benchmark stamps its recorded counter traffic with a hash
 // of every file in csrc/; libksa.so keeps its own copies of fail, HIP_OK and DeviceGuard there.
 //
-// Everything here has internal linkage, and has to: the six libraries are loaded into one process, and a symbol of default
+// Everything here has internal linkage, and has to: the libraries are loaded into one process, and a symbol of default
 // visibility (an inline thread-local above all) would be unified across them by the dynamic loader, so that one library's
 // k??_last_error() returned another's message.  Each library that includes this file gets its own g_err.
 #pragma once
@@ -59,6 +59,19 @@ int check_taps(int T, const float* taps) {
 
 // bytes of one I,Q pair in the sample formats every header numbers alike: complex64 0, uint8 1, int8 2, int16 3
 int iq_sample_bytes(int fmt) { return fmt == 0 ? 8 : fmt == 3 ? 4 : 2; }
+
+// the checks of k??_create that read alike in every library, with the one text each: the format first, the other two last
+// before the first HIP call.  A library that calls the first two asserts that its header's K??_FMT_* are these numbers.
+int check_iq_format(int fmt) { return fmt < 0 || fmt > 3 ? fail("unknown sample format %d", fmt) : 0; }
+
+int check_u8_scaling(int fmt, float u8_offset, float u8_scale) {   // only the uint8 format reads the two
+  if (fmt != 1) return 0;
+  if (!std::isfinite(u8_scale) || u8_scale == 0.f) return fail("u8_scale %g must be finite and non-zero", (double)u8_scale);
+  if (!std::isfinite(u8_offset)) return fail("u8_offset %g must be finite", (double)u8_offset);
+  return 0;
+}
+
+int check_device(int device) { return device < 0 ? fail("device %d must be >= 0", device) : 0; }
 
 int check_iq_aligned(const void* iq, int bytes) {
   if (reinterpret_cast<uintptr_t>(iq) % (unsigned)bytes) return fail("input pointer is not aligned to the %d bytes of a sample", bytes);

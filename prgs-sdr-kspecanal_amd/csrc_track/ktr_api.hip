@@ -136,7 +136,7 @@ int ktr_create(int32_t device, int32_t nbins, int32_t max_spans, int32_t row_gap
   Params par;
   if (int rc = check_params(nbins, row_gap, bin_slop, min_rows, min_spans, &par)) return rc;
   if (capacity < 1 || capacity > KTR_MAX_CAPACITY) return fail("track capacity %d outside 1..%d", capacity, KTR_MAX_CAPACITY);
-  if (device < 0) return fail("device %d must be >= 0", device);
+  if (check_device(device)) return 1;
 
   DeviceGuard dev_guard;
   HIP_OK(hipSetDevice(device));

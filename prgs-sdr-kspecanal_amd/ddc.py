@@ -7,7 +7,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from ._companion import Binding, Companion
+from ._companion import Binding, Companion, host_iq
 from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
 from .engine import DevArray, _ptr, window_table
 
@@ -75,16 +75,12 @@ class DownConverter(Companion):
         self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         self.ntaps = int(self.taps.size)
         inc = phase_inc_for(freq, sampling_rate) if phase_inc is None else int(phase_inc) % 2 ** 64
-        h = C.c_void_p()
-        check(lib().kdc_create(self.device, self.fmt, u8_offset, u8_scale, self.decim, self.ntaps, _ptr(self.taps), inc,
-                               self.max_in, C.byref(h)))
-        self._h = h
+        self._create(self.device, self.fmt, u8_offset, u8_scale, self.decim, self.ntaps, _ptr(self.taps), inc, self.max_in,
+                     stream=stream)
         self.phase_inc = inc
         p, cap = C.c_void_p(), C.c_int64()
         check(lib().kdc_out_dev(self._h, C.byref(p), C.byref(cap)))
         self._out, self.out_capacity = p.value, cap.value
-        if stream is not None:
-            self.set_stream(stream)
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):
@@ -102,16 +98,7 @@ class DownConverter(Companion):
     def process(self, samples):
         """The stream's next samples from host memory (complex64 [n], or [2n] uint8 / int8 / int16 I,Q); complex64 outputs;
         synchronises."""
-        a = np.ascontiguousarray(samples)
-        if self.fmt == FMT_C64:
-            a = np.ascontiguousarray(a, dtype=np.complex64).reshape(-1)
-            n_in = a.size
-        else:
-            want = {FMT_U8: np.uint8, FMT_S8: np.int8, FMT_S16: np.int16}[self.fmt]
-            if a.dtype != want or a.size % 2:
-                raise KsaError("process wants [2n] %s I,Q, got %s %s" % (np.dtype(want), a.dtype, a.shape))
-            a = a.reshape(-1)
-            n_in = a.size // 2
+        a, n_in = host_iq(samples, self.fmt)
         out = np.empty(self.out_count(n_in), dtype=np.complex64)
         n = C.c_int64()
         check(lib().kdc_process(self._h, _ptr(a), n_in, _ptr(out), out.size, C.byref(n)))

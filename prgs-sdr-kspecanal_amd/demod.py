@@ -100,15 +100,11 @@ class Demodulator(Companion):
         self.ntaps = int(self.taps.size)
         self.lead = 1 if self.mode == MODE_FM else 0
         self.dtype = np.dtype(np.int16 if self.out_fmt == OUT_S16 else np.float32)
-        h = C.c_void_p()
-        check(lib().kdm_create(self.device, self.mode, self.decim, self.ntaps, _ptr(self.taps), self.out_fmt, self.pcm_scale,
-                               self.max_in, C.byref(h)))
-        self._h = h
+        self._create(self.device, self.mode, self.decim, self.ntaps, _ptr(self.taps), self.out_fmt, self.pcm_scale, self.max_in,
+                     stream=stream)
         p, cap = C.c_void_p(), C.c_int64()
         check(lib().kdm_out_dev(self._h, C.byref(p), C.byref(cap)))
         self._out, self.out_capacity = p.value, cap.value
-        if stream is not None:
-            self.set_stream(stream)
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):

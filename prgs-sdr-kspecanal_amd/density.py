@@ -51,11 +51,7 @@ class SpectrumDensity(Companion):
         self.levels = int(levels)
         self.lo_db, self.hi_db = float(lo_db), float(hi_db)
         self.device = int(device)
-        h = C.c_void_p()
-        check(lib().ksd_create(self.device, self.nbins, self.width, self.levels, self.lo_db, self.hi_db, C.byref(h)))
-        self._h = h
-        if stream is not None:
-            self.set_stream(stream)
+        self._create(self.device, self.nbins, self.width, self.levels, self.lo_db, self.hi_db, stream=stream)
 
     # -- counting ---------------------------------------------------------------------------------
     def add_rows_dev(self, rows, nrows, row_stride=None):

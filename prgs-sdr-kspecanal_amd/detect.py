@@ -82,12 +82,7 @@ class SignalDetector(Companion):
                  stream=None):
         self.nbins, self.capacity, self.device = int(nbins), int(capacity), int(device)
         self.params = (int(train), int(guard), float(threshold_db), _mode(mode), int(min_width), int(max_gap))
-        h = C.c_void_p()
-        t, g, thr, m, w, k = self.params
-        check(lib().kse_create(self.device, self.nbins, t, g, thr, m, w, k, self.capacity, C.byref(h)))
-        self._h = h
-        if stream is not None:
-            self.set_stream(stream)
+        self._create(self.device, self.nbins, *self.params, self.capacity, stream=stream)
 
     # -- detection --------------------------------------------------------------------------------
     def detect_rows_dev(self, rows, nrows=None, row_stride=None, row_count=None, floor=None):

@@ -7,7 +7,7 @@ import math
 
 import numpy as np
 
-from ._companion import Binding, Companion
+from ._companion import FORMATS, SAMPLE_DTYPES, Binding, Companion, format_of
 from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
 from .engine import DevArray, _ptr
 
@@ -16,8 +16,6 @@ MAX_IN, MAX_COUNT, UNIT = 2 ** 28 - 1, 1 << 30, 1 << 30
 MODE_DC, MODE_IQ = 1, 2
 FLAG_DEGENERATE, FLAG_EMPTY = 1, 2
 MODES = {"dc": MODE_DC, "iq": MODE_IQ, "dc+iq": MODE_DC | MODE_IQ}
-FORMATS = {"c64": FMT_C64, "u8": FMT_U8, "s8": FMT_S8, "s16": FMT_S16}
-SAMPLE_DTYPES = {FMT_C64: np.dtype(np.complex64), FMT_U8: np.dtype(np.uint8), FMT_S8: np.dtype(np.int8), FMT_S16: np.dtype(np.int16)}
 
 _P = C.c_void_p
 _I32, _I64, _F = C.c_int32, C.c_int64, C.c_float
@@ -74,16 +72,10 @@ class IqCorrector(Companion):
     _binding, _info_fields = _bind, ("threads", "lds_bytes", "vgprs", "grid", "tile")
 
     def __init__(self, fmt="c64", max_in=1 << 20, u8_offset=127.5, u8_scale=127.5, device=0, stream=None):
-        if isinstance(fmt, str) and fmt.lower() not in FORMATS:
-            raise KsaError("unknown fmt [%s], expected one of %s" % (fmt, "|".join(FORMATS)))
-        self.fmt = FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
+        self.fmt = format_of(fmt)
         self.max_in, self.device = int(max_in), int(device)
         self.in_dtype = SAMPLE_DTYPES.get(self.fmt, np.dtype(np.complex64))
-        h = C.c_void_p()
-        check(lib().kqf_create(self.device, self.fmt, float(u8_offset), float(u8_scale), self.max_in, C.byref(h)))
-        self._h = h
-        if stream is not None:
-            self.set_stream(stream)
+        self._create(self.device, self.fmt, float(u8_offset), float(u8_scale), self.max_in, stream=stream)
 
     # -- the pass -----------------------------------------------------------------------------------
     def blocks_dev(self, iq, nblocks, block_len, block_stride=None, out=None, out_stride=None, accumulate=False):

@@ -81,12 +81,8 @@ class SpectrumMask(Companion):
         self.min_bins, self.capacity, self.device = int(min_bins), int(capacity), int(device)
         self.upper = _line(upper, self.nbins, "upper")
         self.lower = None if lower is None else _line(lower, self.nbins, "lower")
-        h = C.c_void_p()
-        check(lib().ksm_create(self.device, self.nbins, _ptr(self.upper), None if self.lower is None else _ptr(self.lower),
-                               self.min_bins, self.capacity, C.byref(h)))
-        self._h = h
-        if stream is not None:
-            self.set_stream(stream)
+        self._create(self.device, self.nbins, _ptr(self.upper), None if self.lower is None else _ptr(self.lower),
+                     self.min_bins, self.capacity, stream=stream)
 
     # -- checking ---------------------------------------------------------------------------------
     def check_rows_dev(self, rows, nrows=None, row_stride=None, row_event=None):

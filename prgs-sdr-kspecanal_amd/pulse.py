@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._companion import Binding, Companion
+from ._companion import FORMATS, SAMPLE_DTYPES, Binding, Companion, format_of
 from ._lib import KsaError, FMT_C64, FMT_U8, FMT_S8, FMT_S16
 from .engine import DevArray, _ptr
 
@@ -14,8 +14,6 @@ ABI_VERSION = 1
 MAX_W, MAX_MIN_LEN, MAX_CAPACITY, MAX_IN, MAX_POSITION = 4096, 1 << 20, 1 << 20, 2 ** 28 - 1, 2 ** 52
 POWER_UNIT = 1 << 30                    # q, energy and S count full-scale power in units of 2^-30
 FLAG_OPEN_END = 1
-FORMATS = {"c64": FMT_C64, "u8": FMT_U8, "s8": FMT_S8, "s16": FMT_S16}
-SAMPLE_DTYPES = {FMT_C64: np.dtype(np.complex64), FMT_U8: np.dtype(np.uint8), FMT_S8: np.dtype(np.int8), FMT_S16: np.dtype(np.int16)}
 
 _P = C.c_void_p
 _I32, _I64, _F = C.c_int32, C.c_int64, C.c_float
@@ -67,20 +65,14 @@ class PulseDetector(Companion):
 
     def __init__(self, W=16, on_power=0.1, off_power=None, min_len=1, capacity=1024, max_in=1 << 20, fmt="c64", u8_offset=127.5,
                  u8_scale=127.5, device=0, stream=None):
-        if isinstance(fmt, str) and fmt.lower() not in FORMATS:
-            raise KsaError("unknown fmt [%s], expected one of %s" % (fmt, "|".join(FORMATS)))
-        self.fmt = FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
+        self.fmt = format_of(fmt)
         self.W, self.min_len = int(W), int(min_len)
         self.on_power = float(on_power)
         self.off_power = self.on_power if off_power is None else float(off_power)
         self.capacity, self.max_in, self.device = int(capacity), int(max_in), int(device)
         self.in_dtype = SAMPLE_DTYPES.get(self.fmt, np.dtype(np.complex64))
-        h = C.c_void_p()
-        check(lib().kpl_create(self.device, self.fmt, float(u8_offset), float(u8_scale), self.W, self.on_power, self.off_power,
-                               self.min_len, self.capacity, self.max_in, C.byref(h)))
-        self._h = h
-        if stream is not None:
-            self.set_stream(stream)
+        self._create(self.device, self.fmt, float(u8_offset), float(u8_scale), self.W, self.on_power, self.off_power,
+                     self.min_len, self.capacity, self.max_in, stream=stream)
 
     # -- the stream form ----------------------------------------------------------------------------
     def process_dev(self, iq, n_in, env=None):

@@ -107,15 +107,11 @@ class Resampler(Companion):
         self.taps_per_phase = int(self.taps.size) // self.L
         self.in_dtype = np.dtype(np.complex64 if self.type == TYPE_C64 else np.float32)
         self.dtype = np.dtype(np.int16) if self.out_fmt == OUT_S16 else self.in_dtype
-        h = C.c_void_p()
-        check(lib().krs_create(self.device, self.type, self.L, self.M, self.taps_per_phase, _ptr(self.taps), self.out_fmt,
-                               self.pcm_scale, self.max_in, C.byref(h)))
-        self._h = h
+        self._create(self.device, self.type, self.L, self.M, self.taps_per_phase, _ptr(self.taps), self.out_fmt, self.pcm_scale,
+                     self.max_in, stream=stream)
         p, cap = C.c_void_p(), C.c_int64()
         check(lib().krs_out_dev(self._h, C.byref(p), C.byref(cap)))
         self._out, self.out_capacity = p.value, cap.value
-        if stream is not None:
-            self.set_stream(stream)
 
     # -- the stream form ----------------------------------------------------------------------------
     def out_count(self, n_in):

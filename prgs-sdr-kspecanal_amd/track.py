@@ -86,11 +86,7 @@ class EmissionTracker(Companion):
                  stream=None):
         self.nbins, self.capacity, self.max_spans, self.device = int(nbins), int(capacity), int(max_spans), int(device)
         self.params = (int(row_gap), int(bin_slop), int(min_rows), int(min_spans))
-        h = C.c_void_p()
-        check(lib().ktr_create(self.device, self.nbins, self.max_spans, *self.params, self.capacity, C.byref(h)))
-        self._h = h
-        if stream is not None:
-            self.set_stream(stream)
+        self._create(self.device, self.nbins, self.max_spans, *self.params, self.capacity, stream=stream)
 
     def set_params(self, row_gap=None, bin_slop=None, min_rows=None, min_spans=None):
         """Replace the linking parameters (None keeps a value); they hold from the next link."""

@@ -5,18 +5,16 @@ import importlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import chan_model as cm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import GOLDEN, ROOT, load_pkg
 from test_isa_regression import _asm, _kernels, _resource
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_chan.h")
-LIB = os.path.join(PKG_DIR, "libksa_chan.so")
 GPU_SHAPES = [(2, 1, 1), (2, 2, 3), (4, 4, 2), (8, 2, 3), (16, 1, 4), (64, 4, 2), (32, 1, 32), (256, 2, 8), (512, 2, 16), (1024, 1, 8),
               (1024, 4, 8)]
 SMALL_SHAPES = [(2, 1, 3), (4, 4, 2), (8, 2, 3), (16, 4, 2), (8, 1, 2)]
@@ -36,24 +34,9 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(kch_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_kch.c"
-    src.write_text('#include "ksa_chan.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'int use_kch(void) { kch_chan* h = NULL; return (int)sizeof(table) + KCH_ABI_VERSION + KCH_MAX_TAPS + KCH_FMT_S16 '
-                   '+ KCH_FORM_LDS + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_kch.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("kch_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(("ksa_", "ksd_", "ksm_", "kdc_", "kse_", "kdm_"))], "the companion library must not shadow the others"
-    assert int(re.search(r"#define KCH_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION == X.load().kch_abi_version()
+    text, _ = check_header_exports_binding(BY_MODULE["chan"], X, tmp_path, "typedef kch_chan* handle;\n",
+                                           ["KCH_MAX_TAPS", "KCH_FMT_S16", "KCH_FORM_LDS"])
+    assert X.ABI_VERSION == X.load().kch_abi_version()
     for name, value in (("KCH_MIN_CHAN", X.MIN_CHAN), ("KCH_MAX_CHAN", X.MAX_CHAN), ("KCH_MAX_BRANCH_TAPS", X.MAX_BRANCH_TAPS),
                         ("KCH_MAX_TAPS", X.MAX_TAPS), ("KCH_MAX_IN", X.MAX_IN), ("KCH_FORM_LDS", X.FORM_LDS)):
         assert int(re.search(r"#define %s (\d+)" % name, text).group(1)) == value, name

@@ -1,21 +1,19 @@
-"""Host side of the correlator (no GPU needed): the companion header and library, the binding, the build table, the model every
+"""Host side of the correlator (no GPU needed): the companion header and library, the binding, the model every
 GPU test compares against, the helpers, and the `correlate` / `correlateSave` keys of the command line."""
 import ctypes as C
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import corr_model as cm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import ROOT, load_pkg
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_corr.h")
 LIB = os.path.join(PKG_DIR, "libksa_corr.so")
-OTHERS = ("ksa_", "ksd_", "ksm_", "kdc_", "kse_", "kdm_", "kch_", "krs_")
 
 
 @pytest.fixture(scope="module")
@@ -32,26 +30,10 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(kcr_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_kcr.c"
-    src.write_text('#include "ksa_corr.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'typedef char event_is_36_bytes[sizeof(kcr_event) == 36 ? 1 : -1];\n'
-                   'typedef char block_at_8[offsetof(kcr_event, block) == 8 && offsetof(kcr_event, im) == 32 ? 1 : -1];\n'
-                   'int use_kcr(void) { kcr_corr* h = NULL; return (int)sizeof(table) + KCR_ABI_VERSION + KCR_MAX_K + KCR_FMT_S16 '
-                   '+ (int)(KCR_MAX_POSITION >> 40) + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_kcr.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("kcr_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(OTHERS)], "the companion library must not shadow the others"
-    assert int(re.search(r"#define KCR_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION
+    extra = ('typedef kcr_corr* handle;\ntypedef char event_is_36_bytes[sizeof(kcr_event) == 36 ? 1 : -1];\n'
+             'typedef char block_at_8[offsetof(kcr_event, block) == 8 && offsetof(kcr_event, im) == 32 ? 1 : -1];\n')
+    text, _ = check_header_exports_binding(BY_MODULE["corr"], X, tmp_path, extra,
+                                           ["KCR_MAX_K", "KCR_FMT_S16", "(int)(KCR_MAX_POSITION >> 40)"])
     for name, value in (("KCR_MAX_K", X.MAX_K), ("KCR_MAX_Q", X.MAX_Q), ("KCR_MAX_TEMPLATE_VALUES", X.MAX_TEMPLATE_VALUES),
                         ("KCR_MAX_GUARD", X.MAX_GUARD), ("KCR_MAX_CAPACITY", X.MAX_CAPACITY), ("KCR_MAX_IN", X.MAX_IN),
                         ("KCR_MAX_POSITION", X.MAX_POSITION), ("KCR_FMT_C64", X.FMT_C64), ("KCR_FMT_U8", X.FMT_U8),
@@ -161,35 +143,6 @@ def test_library_loads_without_a_gpu_and_every_create_time_refusal_has_its_own_t
         assert call() != 0 and "null correlator" in lib.kcr_last_error().decode()
     lib.kcr_destroy(None)
     assert len(X.SIGNATURES) == len(calls) + 4          # those, abi_version, last_error, create, destroy
-
-
-def test_the_new_build_table_depends_on_the_shared_directory_and_the_old_tables_are_untouched():
-    load_pkg()
-    build = importlib.import_module("prgs-sdr-kspecanal_amd.build")
-    shared = {os.path.realpath(os.path.join(PKG_DIR, "csrc_shared", f)) for f in ("ksa_host.hpp", "ksa_iq.hpp")}
-    out = os.path.join(build.HERE, "libksa_corr.so")
-    assert list(build.LATER_PRODUCTS) == ["libksa_corr.so"] and list(build.LATER_JOBS) == [out]
-    assert build.TABLES == [build.PRODUCTS, build.MORE_PRODUCTS, build.LATER_PRODUCTS]
-    assert build.JOB_TABLES == [build.JOBS, build.MORE_JOBS, build.LATER_JOBS]
-    src, extra, deps = build.LATER_JOBS[out]
-    deps = {os.path.realpath(f) for f in deps()}
-    assert src == os.path.join(build.HERE, "csrc_corr", "kcr_api.hip") and extra == []
-    assert shared <= deps and os.path.realpath(HEADER) in deps
-    assert {os.path.realpath(os.path.join(PKG_DIR, "csrc_corr", f)) for f in ("kcr_api.hip", "kcr_kernels.hpp")} <= deps
-    assert len(build.JOBS) == 8 and out not in build.JOBS and out not in build.MORE_JOBS
-    assert list(build.MORE_PRODUCTS) == ["libksa_resamp.so"]
-    assert build.is_stale(out) in (False, True) and build.is_stale(os.path.join(build.HERE, "no_such_libksa_corr.so"))
-    # every product of every table is known to _sources, and a product belongs to one table
-    names = [n for table in build.TABLES for n in table]
-    assert len(names) == len(set(names)) == 10
-    for n in names:
-        assert build._sources(n)
-    # the shared pieces are used, not copied
-    for f in ("kcr_api.hip", "kcr_kernels.hpp"):
-        text = open(os.path.join(PKG_DIR, "csrc_corr", f)).read()
-        assert "struct DeviceGuard" not in text and "thread_local" not in text and "unpack_s16(" not in text
-    assert '#include "../csrc_shared/ksa_host.hpp"' in open(os.path.join(PKG_DIR, "csrc_corr", "kcr_api.hip")).read()
-    assert '#include "../csrc_shared/ksa_iq.hpp"' in open(os.path.join(PKG_DIR, "csrc_corr", "kcr_kernels.hpp")).read()
 
 
 # ------------------------------------------------------------------------------------------ the model checks itself

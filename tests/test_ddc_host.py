@@ -5,18 +5,16 @@ import importlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import ddc_model as dm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import GOLDEN, ROOT, load_pkg
 from test_isa_regression import _asm, _kernels, _resource
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_ddc.h")
-LIB = os.path.join(PKG_DIR, "libksa_ddc.so")
 SHAPES = [(1, 1), (1, 33), (2, 16), (3, 11), (4, 32), (5, 35), (16, 128), (64, 1024), (1024, 16384)]
 INC = round(0.1234567 * 2 ** 64)
 
@@ -35,24 +33,8 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(kdc_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_kdc.c"
-    src.write_text('#include "ksa_ddc.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'int use_kdc(void) { kdc_ddc* h = NULL; return (int)sizeof(table) + KDC_ABI_VERSION + KDC_MAX_TAPS + KDC_FMT_S16 '
-                   '+ KDC_FORM_REDUCE + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_kdc.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("kdc_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(("ksa_", "ksd_", "ksm_"))], "the companion library must not shadow the others"
-    assert int(re.search(r"#define KDC_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION
+    text, _ = check_header_exports_binding(BY_MODULE["ddc"], X, tmp_path, "typedef kdc_ddc* handle;\n",
+                                           ["KDC_MAX_TAPS", "KDC_FMT_S16", "KDC_FORM_REDUCE"])
     for name, value in (("KDC_MAX_DECIM", X.MAX_DECIM), ("KDC_MAX_TAPS", X.MAX_TAPS), ("KDC_MAX_IN", X.MAX_IN),
                         ("KDC_FORM_TILE", X.FORM_TILE), ("KDC_FORM_REDUCE", X.FORM_REDUCE)):
         assert int(re.search(r"#define %s (\d+)" % name, text).group(1)) == value, name

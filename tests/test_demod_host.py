@@ -5,19 +5,17 @@ import importlib
 import json
 import os
 import re
-import subprocess
 import wave
 
 import numpy as np
 import pytest
 
 import demod_model as mm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import GOLDEN, ROOT, load_pkg
 from test_isa_regression import _asm, _kernels, _resource
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_demod.h")
-LIB = os.path.join(PKG_DIR, "libksa_demod.so")
 EMU_SHAPES = [(1, 1), (1, 33), (2, 16), (5, 80), (64, 1024), (50, 4096)]
 MODES = (mm.MODE_AM, mm.MODE_FM, mm.MODE_PM)
 
@@ -36,25 +34,8 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(kdm_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_kdm.c"
-    src.write_text('#include "ksa_demod.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'int use_kdm(void) { kdm_demod* h = NULL; return (int)sizeof(table) + KDM_ABI_VERSION + KDM_MAX_TAPS + KDM_MODE_PM '
-                   '+ KDM_OUT_S16 + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_kdm.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("kdm_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(("ksa_", "ksd_", "ksm_", "kdc_", "kse_"))], \
-        "the companion library must not shadow the others"
-    assert int(re.search(r"#define KDM_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION
+    text, _ = check_header_exports_binding(BY_MODULE["demod"], X, tmp_path, "typedef kdm_demod* handle;\n",
+                                           ["KDM_MAX_TAPS", "KDM_MODE_PM", "KDM_OUT_S16"])
     for name, value in (("KDM_MAX_DECIM", X.MAX_DECIM), ("KDM_MAX_TAPS", X.MAX_TAPS), ("KDM_MAX_IN", X.MAX_IN),
                         ("KDM_MODE_AM", X.MODE_AM), ("KDM_MODE_FM", X.MODE_FM), ("KDM_MODE_PM", X.MODE_PM),
                         ("KDM_OUT_F32", X.OUT_F32), ("KDM_OUT_S16", X.OUT_S16)):

@@ -3,19 +3,16 @@ float32 model every GPU test compares against, the command line keys, and the ad
 import importlib
 import json
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import density_model as dm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import GOLDEN, ROOT, load_pkg
 from test_isa_regression import _asm, _find, _kernels, _mix, _resource
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_density.h")
-LIB = os.path.join(PKG_DIR, "libksa_density.so")
 
 
 @pytest.fixture(scope="module")
@@ -32,23 +29,7 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(D, tmp_path):
-    names = sorted(set(re.findall(r"\b(ksd_[a-z0-9_]+)\s*\(", open(HEADER).read())))
-    src = tmp_path / "use_ksd.c"
-    src.write_text('#include "ksa_density.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'int use_ksd(void) { ksd_density* d = NULL; return (int)sizeof(table) + KSD_ABI_VERSION + KSD_MAX_LEVELS + (d != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_ksd.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("ksd_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(D.SIGNATURES) == set(names), set(D.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith("ksa_")], "the companion library must not shadow libksa's entry points"
-    m = re.search(r"#define KSD_ABI_VERSION (\d+)", open(HEADER).read())
-    assert int(m.group(1)) == D.ABI_VERSION
+    check_header_exports_binding(BY_MODULE["density"], D, tmp_path, "typedef ksd_density* handle;\n", ["KSD_MAX_LEVELS"])
 
 
 def test_the_frozen_boundary_is_untouched(D):

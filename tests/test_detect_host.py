@@ -5,18 +5,16 @@ import importlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import detect_model as dm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import GOLDEN, ROOT, load_pkg
 from test_isa_regression import _asm, _kernels, _resource
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_detect.h")
-LIB = os.path.join(PKG_DIR, "libksa_detect.so")
 F = np.float32(-90.0)                      # the floor of the hand-written rows
 STEP = np.float32(1.0 / 64.0)              # one quantisation step
 
@@ -35,28 +33,13 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(kse_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_kse.c"
-    src.write_text('#include "ksa_detect.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'typedef char size_is_32[sizeof(kse_emission) == 32 ? 1 : -1];\n'
-                   + "".join('typedef char off_%s[offsetof(kse_emission, %s) == %d ? 1 : -1];\n' % (f, f, o) for f, o in
-                             (("row", 0), ("bin_lo", 8), ("bin_hi", 12), ("peak_bin", 16), ("ndet", 20), ("peak_db", 24),
-                              ("floor_db", 28))) +
-                   'int use_kse(void) { kse_detector* d = NULL; return (int)sizeof(table) + KSE_ABI_VERSION + KSE_MAX_CAPACITY '
-                   '+ KSE_MODE_CA + KSE_MODE_GO + KSE_MODE_SO + (d != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_kse.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("kse_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(("ksa_", "ksd_", "ksm_", "kdc_"))], "the companion library must not shadow the others"
-    assert "KSE_ABI_VERSION 1" in text and int(re.search(r"#define KSE_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION == 1
+    extra = ('typedef kse_detector* handle;\ntypedef char size_is_32[sizeof(kse_emission) == 32 ? 1 : -1];\n'
+             + "".join('typedef char off_%s[offsetof(kse_emission, %s) == %d ? 1 : -1];\n' % (f, f, o) for f, o in
+                       (("row", 0), ("bin_lo", 8), ("bin_hi", 12), ("peak_bin", 16), ("ndet", 20), ("peak_db", 24),
+                        ("floor_db", 28))))
+    text, _ = check_header_exports_binding(BY_MODULE["detect"], X, tmp_path, extra,
+                                           ["KSE_MAX_CAPACITY", "KSE_MODE_CA", "KSE_MODE_GO", "KSE_MODE_SO"])
+    assert "KSE_ABI_VERSION 1" in text and X.ABI_VERSION == 1
     for name, value in (("KSE_MODE_CA", 0), ("KSE_MODE_GO", 1), ("KSE_MODE_SO", 2), ("KSE_MIN_NBINS", X.MIN_NBINS),
                         ("KSE_MAX_NBINS", X.MAX_NBINS), ("KSE_MAX_TRAIN", X.MAX_TRAIN), ("KSE_MAX_GUARD", X.MAX_GUARD),
                         ("KSE_MAX_GAP", X.MAX_GAP), ("KSE_MAX_CAPACITY", X.MAX_CAPACITY)):

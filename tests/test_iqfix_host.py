@@ -1,23 +1,21 @@
 """Host side of the IQ corrector (no GPU needed): the model every GPU test compares against on hand-worked cases and on the
-definition's purpose, the companion header and library, the binding, the build table, and the `iqfix` / `iqfixSave` keys of the
+definition's purpose, the companion header and library, the binding, and the `iqfix` / `iqfixSave` keys of the
 command line."""
 import ctypes as C
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import iqfix_model as qm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import ROOT, load_pkg
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_iqfix.h")
 LIB = os.path.join(PKG_DIR, "libksa_iqfix.so")
 SRC_DIR = os.path.join(PKG_DIR, "csrc_iqfix")
-OTHERS = ("ksa_", "ksd_", "ksm_", "kdc_", "kse_", "kdm_", "kch_", "krs_", "kcr_", "kpl_", "ktr_")
 F32 = np.float32
 
 
@@ -162,28 +160,16 @@ def _ctype_of(X, param):
 
 
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
+    extra = ('typedef kqf_corrector* handle;\ntypedef char coeffs_are_32_bytes[sizeof(kqf_coeffs) == 32 ? 1 : -1];\n'
+             + "".join('typedef char %s_at_%d[offsetof(kqf_coeffs, %s) == %d ? 1 : -1];\n' % (f, o, f, o)
+                       for f, o in (("dc_i", 0), ("dc_q", 4), ("c", 8), ("d", 12), ("flags", 16), ("mode", 20), ("count", 24))))
+    text, names = check_header_exports_binding(BY_MODULE["iqfix"], X, tmp_path, extra,
+                                               ["KQF_FMT_S16", "KQF_MAX_IN", "KQF_MODE_DC", "KQF_MODE_IQ", "KQF_FLAG_DEGENERATE",
+                                                "KQF_FLAG_EMPTY"])
     protos = re.findall(r"^(int|void|const char\*) (kqf_[a-z0-9_]+)\((.*?)\);", text, re.M | re.S)
-    names = sorted(n for _, n, _ in protos)
+    assert names == sorted(n for _, n, _ in protos)                # every name the header holds is a declaration of this shape
     assert names == sorted(set(re.findall(r"\b(kqf_[a-z0-9_]+)\s*\(", text.split("#ifndef KSA_IQFIX_H")[1])))
-    src = tmp_path / "use_kqf.c"
-    src.write_text('#include "ksa_iqfix.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'typedef char coeffs_are_32_bytes[sizeof(kqf_coeffs) == 32 ? 1 : -1];\n'
-                   + "".join('typedef char %s_at_%d[offsetof(kqf_coeffs, %s) == %d ? 1 : -1];\n' % (f, o, f, o)
-                             for f, o in (("dc_i", 0), ("dc_q", 4), ("c", 8), ("d", 12), ("flags", 16), ("mode", 20), ("count", 24)))
-                   + 'int use_kqf(void) { kqf_corrector* h = NULL; return (int)sizeof(table) + KQF_ABI_VERSION + KQF_FMT_S16 + KQF_MAX_IN '
-                   '+ KQF_MODE_DC + KQF_MODE_IQ + KQF_FLAG_DEGENERATE + KQF_FLAG_EMPTY + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_kqf.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    assert {s for s in symbols if s.startswith("kqf_")} == set(names)
-    assert not [s for s in symbols if s.startswith(OTHERS)], "the companion library must not shadow the others"
     # the binding's signatures are the header's declarations, argument by argument
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
     for ret, name, params in protos:
         res, args = X.SIGNATURES[name]
         assert res == {"int": C.c_int, "void": None, "const char*": C.c_char_p}[ret], name
@@ -298,38 +284,6 @@ def test_per_call_refusals_stand_before_the_first_hip_call():
         assert "fail(" not in body[end:].replace("return fail(\"hipMalloc", ""), name
     assert "#pragma clang fp contract(off)" in _body(text, "solve_sums")
     assert "getenv" not in text
-
-
-def test_the_iqfix_build_table_is_new_and_the_old_tables_and_lists_are_untouched():
-    load_pkg()
-    build = importlib.import_module("prgs-sdr-kspecanal_amd.build")
-    out = os.path.join(build.HERE, "libksa_iqfix.so")
-    assert build.IQFIX_PRODUCTS == {"libksa_iqfix.so": ("csrc_iqfix", "kqf_api.hip", "ksa_iqfix.h", [])}
-    assert list(build.IQFIX_JOBS) == [out]
-    assert build.WHOLE_TABLES == build.EVERY_TABLES + [build.IQFIX_PRODUCTS]
-    assert build.WHOLE_JOB_TABLES == build.EVERY_JOB_TABLES + [build.IQFIX_JOBS]
-    assert build.TABLES == [build.PRODUCTS, build.MORE_PRODUCTS, build.LATER_PRODUCTS]
-    assert build.ALL_TABLES == build.TABLES + [build.PULSE_PRODUCTS] and build.EVERY_TABLES == build.ALL_TABLES + [build.TRACK_PRODUCTS]
-    assert build.JOB_TABLES == [build.JOBS, build.MORE_JOBS, build.LATER_JOBS]
-    assert build.ALL_JOB_TABLES == build.JOB_TABLES + [build.PULSE_JOBS]
-    assert build.EVERY_JOB_TABLES == build.ALL_JOB_TABLES + [build.TRACK_JOBS]
-    assert list(build.PRODUCTS) == ["libksa.so", "libksa_exp.so", "libksa_density.so", "libksa_mask.so", "libksa_ddc.so",
-                                    "libksa_detect.so", "libksa_demod.so", "libksa_chan.so"]
-    assert [list(t) for t in build.EVERY_TABLES[1:]] == [["libksa_resamp.so"], ["libksa_corr.so"], ["libksa_pulse.so"], ["libksa_track.so"]]
-    assert not any(out in jobs for jobs in build.EVERY_JOB_TABLES) and not any("libksa_iqfix.so" in t for t in build.EVERY_TABLES)
-    names = [n for table in build.WHOLE_TABLES for n in table]
-    assert len([n for table in build.EVERY_TABLES for n in table]) == 12 and len(names) == len(set(names)) == 13
-    for n in names:
-        assert build._sources(n)
-    src, extra, deps = build.IQFIX_JOBS[out]
-    deps = {os.path.realpath(f) for f in deps()}
-    assert src == os.path.join(build.HERE, "csrc_iqfix", "kqf_api.hip") and extra == []
-    shared = {os.path.realpath(os.path.join(PKG_DIR, "csrc_shared", f)) for f in ("ksa_host.hpp", "ksa_iq.hpp")}
-    assert shared <= deps and os.path.realpath(HEADER) in deps
-    assert {os.path.realpath(os.path.join(SRC_DIR, f)) for f in ("kqf_api.hip", "kqf_kernels.hpp")} <= deps
-    assert build.is_stale(out) in (False, True) and build.is_stale(os.path.join(build.HERE, "no_such_libksa_iqfix.so"))
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "IQFIX_PRODUCTS" in entry and "libksa_iqfix.so" in entry and "WHOLE_TABLES" in entry
 
 
 def test_the_shared_headers_are_included_not_copied_and_no_atomic_exists():

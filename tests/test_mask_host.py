@@ -5,18 +5,16 @@ import importlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import mask_model as mm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import GOLDEN, ROOT, load_pkg
 from test_isa_regression import _asm, _kernels, _resource
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_mask.h")
-LIB = os.path.join(PKG_DIR, "libksa_mask.so")
 
 
 @pytest.fixture(scope="module")
@@ -33,28 +31,11 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(M, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(ksm_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_ksm.c"
-    src.write_text('#include "ksa_mask.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'typedef char size_is_32[sizeof(ksm_event) == 32 ? 1 : -1];\n'
-                   + "".join('typedef char off_%s[offsetof(ksm_event, %s) == %d ? 1 : -1];\n' % (f, f, o) for f, o in
-                             (("row", 0), ("nover", 8), ("nunder", 12), ("nnan", 16), ("peak_bin", 20), ("peak_excess", 24),
-                              ("peak_kind", 28))) +
-                   'int use_ksm(void) { ksm_mask* m = NULL; return (int)sizeof(table) + KSM_ABI_VERSION + KSM_MAX_CAPACITY + (m != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_ksm.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("ksm_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(M.SIGNATURES) == set(names), set(M.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(("ksa_", "ksd_"))], "the companion library must not shadow the other libraries"
-    m = re.search(r"#define KSM_ABI_VERSION (\d+)", text)
-    assert int(m.group(1)) == M.ABI_VERSION
+    extra = ('typedef ksm_mask* handle;\ntypedef char size_is_32[sizeof(ksm_event) == 32 ? 1 : -1];\n'
+             + "".join('typedef char off_%s[offsetof(ksm_event, %s) == %d ? 1 : -1];\n' % (f, f, o) for f, o in
+                       (("row", 0), ("nover", 8), ("nunder", 12), ("nnan", 16), ("peak_bin", 20), ("peak_excess", 24),
+                        ("peak_kind", 28))))
+    check_header_exports_binding(BY_MODULE["mask"], M, tmp_path, extra, ["KSM_MAX_CAPACITY"])
     assert M.EVENT_DTYPE == mm.EVENT_DTYPE and M.EVENT_DTYPE.itemsize == 32
     assert [M.EVENT_DTYPE.fields[n][1] for n in M.EVENT_DTYPE.names] == [0, 8, 12, 16, 20, 24, 28]
 

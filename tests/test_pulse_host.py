@@ -1,21 +1,19 @@
-"""Host side of the pulse detector (no GPU needed): the companion header and library, the binding, the build table, the model
+"""Host side of the pulse detector (no GPU needed): the companion header and library, the binding, the model
 every GPU test compares against on hand-worked cases, and the `pulses` / `pulsesSave` keys of the command line."""
 import ctypes as C
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import pulse_model as pm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import ROOT, load_pkg
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_pulse.h")
 LIB = os.path.join(PKG_DIR, "libksa_pulse.so")
-OTHERS = ("ksa_", "ksd_", "ksm_", "kdc_", "kse_", "kdm_", "kch_", "krs_", "kcr_")
 OFFSETS = {"start": 0, "len": 8, "energy": 16, "peak": 24, "peak_pos": 32, "dre": 40, "dim": 48, "block": 56, "flags": 60}
 
 
@@ -33,26 +31,11 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(kpl_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_kpl.c"
-    src.write_text('#include "ksa_pulse.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'typedef char record_is_64_bytes[sizeof(kpl_pulse) == 64 ? 1 : -1];\n'
-                   + "".join('typedef char %s_at_%d[offsetof(kpl_pulse, %s) == %d ? 1 : -1];\n' % (f, o, f, o) for f, o in OFFSETS.items())
-                   + 'int use_kpl(void) { kpl_detector* h = NULL; return (int)sizeof(table) + KPL_ABI_VERSION + KPL_MAX_W + KPL_FMT_S16 '
-                   '+ (int)(KPL_MAX_POSITION >> 40) + KPL_FLAG_OPEN_END + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_kpl.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("kpl_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(OTHERS)], "the companion library must not shadow the others"
-    assert int(re.search(r"#define KPL_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION == 1
+    extra = ('typedef kpl_detector* handle;\ntypedef char record_is_64_bytes[sizeof(kpl_pulse) == 64 ? 1 : -1];\n'
+             + "".join('typedef char %s_at_%d[offsetof(kpl_pulse, %s) == %d ? 1 : -1];\n' % (f, o, f, o) for f, o in OFFSETS.items()))
+    text, _ = check_header_exports_binding(BY_MODULE["pulse"], X, tmp_path, extra,
+                                           ["KPL_MAX_W", "KPL_FMT_S16", "(int)(KPL_MAX_POSITION >> 40)", "KPL_FLAG_OPEN_END"])
+    assert X.ABI_VERSION == 1
     for name, value in (("KPL_MAX_W", X.MAX_W), ("KPL_MAX_MIN_LEN", X.MAX_MIN_LEN), ("KPL_MAX_CAPACITY", X.MAX_CAPACITY),
                         ("KPL_MAX_IN", X.MAX_IN), ("KPL_MAX_POSITION", X.MAX_POSITION), ("KPL_POWER_UNIT", X.POWER_UNIT),
                         ("KPL_FLAG_OPEN_END", X.FLAG_OPEN_END), ("KPL_FMT_C64", X.FMT_C64), ("KPL_FMT_U8", X.FMT_U8),
@@ -155,40 +138,10 @@ def test_library_loads_without_a_gpu_and_every_create_time_refusal_has_its_own_t
     assert len(X.SIGNATURES) == len(calls) + 4          # those, abi_version, last_error, create, destroy
 
 
-def test_the_pulse_build_table_depends_on_the_shared_directory_and_the_old_tables_are_untouched():
-    load_pkg()
-    build = importlib.import_module("prgs-sdr-kspecanal_amd.build")
-    shared = {os.path.realpath(os.path.join(PKG_DIR, "csrc_shared", f)) for f in ("ksa_host.hpp", "ksa_iq.hpp")}
-    out = os.path.join(build.HERE, "libksa_pulse.so")
-    assert build.PULSE_PRODUCTS == {"libksa_pulse.so": ("csrc_pulse", "kpl_api.hip", "ksa_pulse.h", [])}
-    assert list(build.PULSE_JOBS) == [out]
-    assert build.TABLES == [build.PRODUCTS, build.MORE_PRODUCTS, build.LATER_PRODUCTS]
-    assert build.JOB_TABLES == [build.JOBS, build.MORE_JOBS, build.LATER_JOBS]
-    assert build.ALL_TABLES == build.TABLES + [build.PULSE_PRODUCTS]
-    assert build.ALL_JOB_TABLES == build.JOB_TABLES + [build.PULSE_JOBS]
-    assert list(build.LATER_PRODUCTS) == ["libksa_corr.so"] and list(build.MORE_PRODUCTS) == ["libksa_resamp.so"]
-    src, extra, deps = build.PULSE_JOBS[out]
-    deps = {os.path.realpath(f) for f in deps()}
-    assert src == os.path.join(build.HERE, "csrc_pulse", "kpl_api.hip") and extra == []
-    assert shared <= deps and os.path.realpath(HEADER) in deps
-    assert {os.path.realpath(os.path.join(PKG_DIR, "csrc_pulse", f)) for f in ("kpl_api.hip", "kpl_kernels.hpp")} <= deps
-    assert not any(out in jobs for jobs in build.JOB_TABLES)
-    assert build.is_stale(out) in (False, True) and build.is_stale(os.path.join(build.HERE, "no_such_libksa_corr.so"))
-    # every product of every table is known to _sources, and a product belongs to one table
-    assert len([n for table in build.TABLES for n in table]) == 10
-    names = [n for table in build.ALL_TABLES for n in table]
-    assert len(names) == len(set(names)) == 11
-    for n in names:
-        assert build._sources(n)
-    # the shared pieces are used, not copied
+def test_the_pulse_sources_hold_no_atomic():
     for f in ("kpl_api.hip", "kpl_kernels.hpp"):
         text = open(os.path.join(PKG_DIR, "csrc_pulse", f)).read()
-        assert "struct DeviceGuard" not in text and "thread_local" not in text and "unpack_s16(" not in text
         assert "atomic" not in text.replace("no atomic is involved", "")
-    assert '#include "../csrc_shared/ksa_host.hpp"' in open(os.path.join(PKG_DIR, "csrc_pulse", "kpl_api.hip")).read()
-    assert '#include "../csrc_shared/ksa_iq.hpp"' in open(os.path.join(PKG_DIR, "csrc_pulse", "kpl_kernels.hpp")).read()
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "PULSE_PRODUCTS" in entry and "libksa_pulse.so" in entry
 
 
 # ------------------------------------------------------------------------------------------ the model on hand-worked cases

@@ -1,23 +1,20 @@
-"""Host side of the resampler (no GPU needed): the companion header and library, the binding, the build table, the models every
+"""Host side of the resampler (no GPU needed): the companion header and library, the binding, the models every
 GPU test compares against, the helpers, the `audioRate` key of the command line, and the kernels' resource report."""
 import ctypes as C
 import importlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import resamp_model as rm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import GOLDEN, ROOT, load_pkg
 from test_isa_regression import _asm, _kernels, _resource
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_resamp.h")
-LIB = os.path.join(PKG_DIR, "libksa_resamp.so")
-OTHERS = ("ksa_", "ksd_", "ksm_", "kdc_", "kse_", "kdm_", "kch_")
 PAIRS = [(3, 16), (147, 160), (160, 147), (1, 16), (24, 125), (3, 2), (2, 3), (1024, 1023), (1024, 1), (147, 800), (64, 1023), (5, 16)]
 EMU_SHAPES = [(1, 1, 1), (1, 3, 4), (3, 1, 4), (2, 3, 5), (3, 2, 8), (147, 160, 12), (160, 147, 8), (1024, 1023, 8), (1024, 1, 16),
               (64, 1023, 256), (1, 16, 128)]
@@ -37,24 +34,8 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(krs_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_krs.c"
-    src.write_text('#include "ksa_resamp.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'int use_krs(void) { krs_resamp* h = NULL; return (int)sizeof(table) + KRS_ABI_VERSION + KRS_MAX_TAPS + KRS_TYPE_C64 '
-                   '+ KRS_OUT_S16 + (int)(KRS_MAX_POSITION >> 40) + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_krs.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("krs_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(OTHERS)], "the companion library must not shadow the others"
-    assert int(re.search(r"#define KRS_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION
+    text, _ = check_header_exports_binding(BY_MODULE["resamp"], X, tmp_path, "typedef krs_resamp* handle;\n",
+                                           ["KRS_MAX_TAPS", "KRS_TYPE_C64", "KRS_OUT_S16", "(int)(KRS_MAX_POSITION >> 40)"])
     for name, value in (("KRS_MAX_L", X.MAX_L), ("KRS_MAX_M", X.MAX_M), ("KRS_MAX_RATIO", X.MAX_RATIO),
                         ("KRS_MAX_PHASE_TAPS", X.MAX_PHASE_TAPS), ("KRS_MAX_TAPS", X.MAX_TAPS), ("KRS_MAX_IN", X.MAX_IN),
                         ("KRS_MAX_POSITION", X.MAX_POSITION), ("KRS_TYPE_F32", X.TYPE_F32), ("KRS_TYPE_C64", X.TYPE_C64),
@@ -149,28 +130,6 @@ def test_library_loads_without_a_gpu_and_there_is_no_fallback(X):
         assert call() != 0 and "null resampler" in lib.krs_last_error().decode()
     lib.krs_destroy(None)
     assert len(X.SIGNATURES) == len(calls) + 4          # those, abi_version, last_error, create, destroy
-
-
-def test_the_new_build_table_depends_on_the_shared_directory_and_libksa_does_not():
-    load_pkg()
-    build = importlib.import_module("prgs-sdr-kspecanal_amd.build")
-    shared = {os.path.realpath(os.path.join(PKG_DIR, "csrc_shared", f)) for f in ("ksa_host.hpp", "ksa_iq.hpp")}
-    out = os.path.join(build.HERE, "libksa_resamp.so")
-    assert list(build.MORE_PRODUCTS) == ["libksa_resamp.so"] and list(build.MORE_JOBS) == [out]
-    src, extra, deps = build.MORE_JOBS[out]
-    deps = {os.path.realpath(f) for f in deps()}
-    assert src == os.path.join(build.HERE, "csrc_resamp", "krs_api.hip") and extra == []
-    assert shared <= deps and os.path.realpath(HEADER) in deps
-    assert {os.path.realpath(os.path.join(PKG_DIR, "csrc_resamp", f)) for f in ("krs_api.hip", "krs_kernels.hpp")} <= deps
-    assert len(build.JOBS) == 8 and out not in build.JOBS
-    for o in (build.OUT, build.OUT_EXP):
-        assert not [f for f in build.JOBS[o][2]() if "csrc_shared" in f or "csrc_resamp" in f], o
-    assert build.is_stale(out) in (False, True) and build.is_stale(os.path.join(build.HERE, "no_such_libksa_resamp.so"))
-    # the shared pieces are used, not copied
-    for f in ("krs_api.hip", "krs_kernels.hpp"):
-        text = open(os.path.join(PKG_DIR, "csrc_resamp", f)).read()
-        assert "struct DeviceGuard" not in text and "thread_local" not in text
-    assert '#include "../csrc_shared/ksa_host.hpp"' in open(os.path.join(PKG_DIR, "csrc_resamp", "krs_api.hip")).read()
 
 
 # ------------------------------------------------------------------------------------------ the model checks itself

@@ -1,21 +1,19 @@
-"""Host side of the emission tracker (no GPU needed): the companion header and library, the binding, the build tables, the
+"""Host side of the emission tracker (no GPU needed): the companion header and library, the binding, the
 model every GPU test compares against on hand-worked cases, and the `track` / `trackSave` keys of the command line."""
 import ctypes as C
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import track_model as tm
+from companion_helper import BY_MODULE, check_header_exports_binding
 from conftest import ROOT, load_pkg
 
 PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
-HEADER = os.path.join(ROOT, "include", "ksa_track.h")
 LIB = os.path.join(PKG_DIR, "libksa_track.so")
-OTHERS = ("ksa_", "ksd_", "ksm_", "kdc_", "kse_", "kdm_", "kch_", "krs_", "kcr_", "kpl_")
 OFFSETS = {"row_first": 0, "row_last": 8, "peak_row": 16, "cells": 24, "sum_mid2": 32, "bin_lo": 40, "bin_hi": 44, "nspans": 48,
            "peak_bin": 52, "mid2_first": 56, "mid2_last": 60, "first_span": 64, "flags": 68, "peak_db": 72, "floor_db": 76}
 SPAN_OFFSETS = {"row": 0, "bin_lo": 8, "bin_hi": 12, "peak_bin": 16, "ndet": 20, "peak_db": 24, "floor_db": 28}
@@ -35,28 +33,13 @@ def K():
 
 # ------------------------------------------------------------------------------------------ header, exports, binding
 def test_header_is_c99_and_matches_the_exports_and_the_binding(X, tmp_path):
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r"\b(ktr_[a-z0-9_]+)\s*\(", text)))
-    src = tmp_path / "use_ktr.c"
-    src.write_text('#include "ksa_track.h"\n#include <stddef.h>\n'
-                   'typedef void (*fn_t)(void);\nstatic const fn_t table[] = {' + ", ".join("(fn_t)%s" % n for n in names) + '};\n'
-                   'typedef char track_is_80_bytes[sizeof(ktr_track) == 80 ? 1 : -1];\n'
-                   'typedef char span_is_32_bytes[sizeof(ktr_span) == 32 ? 1 : -1];\n'
-                   + "".join('typedef char t_%s_at_%d[offsetof(ktr_track, %s) == %d ? 1 : -1];\n' % (f, o, f, o) for f, o in OFFSETS.items())
-                   + "".join('typedef char s_%s_at_%d[offsetof(ktr_span, %s) == %d ? 1 : -1];\n' % (f, o, f, o) for f, o in SPAN_OFFSETS.items())
-                   + 'int use_ktr(void) { ktr_tracker* h = NULL; return (int)sizeof(table) + KTR_ABI_VERSION + KTR_MAX_ROW_GAP '
-                   '+ KTR_MAX_NBINS + KTR_MAX_SPANS + KTR_MAX_CAPACITY + KTR_FLAG_OPEN_END + (h != NULL); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "use_ktr.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    symbols = [ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln]
-    exported = {s for s in symbols if s.startswith("ktr_")}
-    assert exported == set(names), exported ^ set(names)
-    assert set(X.SIGNATURES) == set(names), set(X.SIGNATURES) ^ set(names)
-    assert not [s for s in symbols if s.startswith(OTHERS)], "the companion library must not shadow the others"
-    assert int(re.search(r"#define KTR_ABI_VERSION (\d+)", text).group(1)) == X.ABI_VERSION == 1
+    extra = ('typedef ktr_tracker* handle;\ntypedef char track_is_80_bytes[sizeof(ktr_track) == 80 ? 1 : -1];\n'
+             'typedef char span_is_32_bytes[sizeof(ktr_span) == 32 ? 1 : -1];\n'
+             + "".join('typedef char t_%s_at_%d[offsetof(ktr_track, %s) == %d ? 1 : -1];\n' % (f, o, f, o) for f, o in OFFSETS.items())
+             + "".join('typedef char s_%s_at_%d[offsetof(ktr_span, %s) == %d ? 1 : -1];\n' % (f, o, f, o) for f, o in SPAN_OFFSETS.items()))
+    text, _ = check_header_exports_binding(BY_MODULE["track"], X, tmp_path, extra,
+                                           ["KTR_MAX_ROW_GAP", "KTR_MAX_NBINS", "KTR_MAX_SPANS", "KTR_MAX_CAPACITY", "KTR_FLAG_OPEN_END"])
+    assert X.ABI_VERSION == 1
     for name, value in (("KTR_MAX_NBINS", X.MAX_NBINS), ("KTR_MAX_SPANS", X.MAX_SPANS), ("KTR_MAX_ROW_GAP", X.MAX_ROW_GAP),
                         ("KTR_MAX_CAPACITY", X.MAX_CAPACITY), ("KTR_FLAG_OPEN_END", X.FLAG_OPEN_END)):
         assert int(re.search(r"#define %s (\d+)" % name, text).group(1)) == value, name
@@ -166,42 +149,11 @@ def test_library_loads_without_a_gpu_and_every_refusal_has_its_own_text(X):
             assert 0 <= body.find(w) < first_hip, (fn, w)
 
 
-def test_the_track_build_table_is_new_and_the_old_tables_are_untouched():
-    load_pkg()
-    build = importlib.import_module("prgs-sdr-kspecanal_amd.build")
-    shared = {os.path.realpath(os.path.join(PKG_DIR, "csrc_shared", f)) for f in ("ksa_host.hpp", "ksa_iq.hpp")}
-    out = os.path.join(build.HERE, "libksa_track.so")
-    assert build.TRACK_PRODUCTS == {"libksa_track.so": ("csrc_track", "ktr_api.hip", "ksa_track.h", [])}
-    assert list(build.TRACK_JOBS) == [out]
-    assert build.EVERY_TABLES == build.ALL_TABLES + [build.TRACK_PRODUCTS]
-    assert build.EVERY_JOB_TABLES == build.ALL_JOB_TABLES + [build.TRACK_JOBS]
-    # the older tables and lists are what they were
-    assert build.TABLES == [build.PRODUCTS, build.MORE_PRODUCTS, build.LATER_PRODUCTS]
-    assert build.JOB_TABLES == [build.JOBS, build.MORE_JOBS, build.LATER_JOBS]
-    assert build.ALL_TABLES == build.TABLES + [build.PULSE_PRODUCTS]
-    assert build.ALL_JOB_TABLES == build.JOB_TABLES + [build.PULSE_JOBS]
-    assert len(build.PRODUCTS) == 8 and list(build.MORE_PRODUCTS) == ["libksa_resamp.so"]
-    assert list(build.LATER_PRODUCTS) == ["libksa_corr.so"] and list(build.PULSE_PRODUCTS) == ["libksa_pulse.so"]
-    assert not any(out in jobs for jobs in build.ALL_JOB_TABLES)
-    names = [n for table in build.EVERY_TABLES for n in table]
-    assert len(names) == len(set(names)) == 12          # eleven libraries and the experiments build
-    for n in names:
-        assert build._sources(n)
-    src, extra, deps = build.TRACK_JOBS[out]
-    deps = {os.path.realpath(f) for f in deps()}
-    assert src == os.path.join(build.HERE, "csrc_track", "ktr_api.hip") and extra == []
-    assert shared <= deps and os.path.realpath(HEADER) in deps
-    assert {os.path.realpath(os.path.join(PKG_DIR, "csrc_track", f)) for f in ("ktr_api.hip", "ktr_kernels.hpp")} <= deps
-    assert build.is_stale(out) in (False, True) and build.is_stale(os.path.join(build.HERE, "no_such_libksa_track.so"))
-    # the shared pieces are used, not copied; the kernels hold no float atomic and name no other library
+def test_the_track_sources_name_no_other_library_and_hold_no_float_atomic():
     for f in ("ktr_api.hip", "ktr_kernels.hpp"):
         text = open(os.path.join(PKG_DIR, "csrc_track", f)).read()
-        assert "struct DeviceGuard" not in text and "thread_local" not in text and "getenv" not in text
         assert "kse_" not in text and "ksa_detect.h" not in text
         assert not re.search(r"atomic\w*\([^;]*float", text)
-    assert '#include "../csrc_shared/ksa_host.hpp"' in open(os.path.join(PKG_DIR, "csrc_track", "ktr_api.hip")).read()
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "TRACK_PRODUCTS" in entry and "libksa_track.so" in entry and "EVERY_TABLES" in entry
 
 
 # ------------------------------------------------------------------------------------------ the model on hand-worked cases
