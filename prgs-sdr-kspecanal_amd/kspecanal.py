@@ -75,6 +75,7 @@ full-width d['Fft.*'] arrays are read from the device when a RAW / CONV plot nee
 DURING such a run they are None / stale (the reference refreshes them after every frame, K:470-476) -- code that reads
 d['Fft.*'] between frames calls _materialize(d, d['ksa.engine'], scan) first.
 """
+import collections
 import pickle
 import signal
 import sys
@@ -239,19 +240,49 @@ def handle_args(d, argv=None):
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] must be >= 1".format(d["frameBatch"]))
     if d["bUsePSD"] and d["frameBatch"] > 1:
         prg_quit(d, "ERROR:handle_args: frameBatch [{}] needs bUsePSD false: the PSD diagnostic is per block".format(d["frameBatch"]))
-    _handle_pfb(d)
-    _handle_density(d)
-    _handle_mask(d)
-    _handle_zoom(d)
-    _handle_channels(d)
-    _handle_detect(d)
-    _handle_demod(d)
-    _handle_resample(d)
-    _handle_correlate(d)
-    _handle_pulses(d)
-    _handle_track(d)
-    _handle_iqfix(d)
+    for handle in _HANDLERS:
+        handle(d)
     return d
+
+
+# ---------------------------------------------------------------------- what the handlers of the additive zeroSpan keys share
+def _key_text(d, key, spec_key, save=None):
+    """Opens a handler: d[spec_key] = None, and the key's text -- or, when the key is off, None after the warning about a save
+    key that was given without it."""
+    d[spec_key] = None
+    if not d[key] and save and d[save]:
+        print("WARN:handle_args: {} [{}] is ignored without {}".format(save, d[save], key))
+    return d[key] or None
+
+
+def _refuse(d, key, text, rule):
+    prg_quit(d, "ERROR:handle_args: {} [{}]: {}".format(key, text, rule))
+
+
+def _gate(d, key, text, psd_reason=None):
+    """Where a zeroSpan-only key may run: True (after the warning) when playback ignores it, a quit in any other mode, and a
+    quit under bUsePSD when the key gives a reason why it cannot run beside the PSD diagnostic."""
+    if d["prgMode"] == "ZEROSPANPLAY":
+        print("WARN:handle_args: {} [{}] is ignored when playing saved spectra".format(key, text))
+        return True
+    if d["prgMode"] != "ZEROSPAN":
+        prg_quit(d, "ERROR:handle_args: {} [{}] is zeroSpan only, prgMode is [{}]".format(key, text, d["prgMode"]))
+    if psd_reason and d["bUsePSD"]:
+        prg_quit(d, "ERROR:handle_args: {} [{}] needs bUsePSD false: {}".format(key, text, psd_reason))
+    return False
+
+
+def _options(parts, spec, names):
+    """The optional name=value suffixes of a key, in any order, each at most once: `names` maps the lower-cased names to the
+    fields of `spec`, whose defaults tell a word from an integer.  ValueError on an unknown name, a missing = or a repeat."""
+    seen = set()
+    for part in parts:
+        name, eq, value = part.partition("=")
+        key = names.get(name.lower())
+        if not eq or key is None or key in seen:
+            raise ValueError(part)
+        seen.add(key)
+        spec[key] = value.lower() if isinstance(spec[key], str) else int(value)
 
 
 DENSITY_RULE = "density wants L:lo:hi with an integer 1 <= L <= 1024 levels and finite lo < hi in dB"
@@ -259,26 +290,18 @@ DENSITY_RULE = "density wants L:lo:hi with an integer 1 <= L <= 1024 levels and 
 
 def _handle_density(d):
     """density L:lo:hi (additive, zeroSpan only): d['density.spec'] = (L, lo, hi), or None when the key is off."""
-    d["density.spec"] = None
-    text = d["density"]
+    text = _key_text(d, "density", "density.spec", "densitySave")
     if not text:
-        if d["densitySave"]:
-            print("WARN:handle_args: densitySave [{}] is ignored without density".format(d["densitySave"]))
         return
     try:
         levels, lo, hi = text.split(":")
         levels, lo, hi = int(levels), float(lo), float(hi)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: density [{}]: {}".format(text, DENSITY_RULE))
+        _refuse(d, "density", text, DENSITY_RULE)
     if not (1 <= levels <= 1024 and np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-        prg_quit(d, "ERROR:handle_args: density [{}]: {}".format(text, DENSITY_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: density [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "density", text, DENSITY_RULE)
+    if _gate(d, "density", text, "it counts the engine's own dB rows"):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: density [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
-    if d["bUsePSD"]:
-        prg_quit(d, "ERROR:handle_args: density [{}] needs bUsePSD false: it counts the engine's own dB rows".format(text))
     d["density.spec"] = (levels, lo, hi)
 
 
@@ -290,32 +313,26 @@ MASK_RULE = ("mask wants flat:U[:L] (dB, L <= U), file:PATH (an .npy of [fftSize
 def _handle_mask(d):
     """mask flat:U[:L] | file:PATH | learn:F:M, with optional :minBins=K and :events=E (additive, zeroSpan only):
     d['mask.spec'] = dict(kind, upper, lower, frames, margin, min_bins, capacity), or None when the key is off."""
-    d["mask.spec"] = None
-    text = d["mask"]
+    text = _key_text(d, "mask", "mask.spec", "maskSave")
     if not text:
-        if d["maskSave"]:
-            print("WARN:handle_args: maskSave [{}] is ignored without mask".format(d["maskSave"]))
         return
 
     def refuse():
-        prg_quit(d, "ERROR:handle_args: mask [{}]: {}".format(text, MASK_RULE))
+        _refuse(d, "mask", text, MASK_RULE)
 
     n = d["fftSize"]
     spec = dict(kind=None, upper=None, lower=None, frames=0, margin=0.0, min_bins=1, capacity=4096)
-    body = text
+    names = {"minbins": "min_bins", "events": "capacity"}
+    body, opts = text, []
     try:
-        seen = set()
-        while True:                                  # the optional suffixes, in either order, each at most once
+        while True:                                  # peeled from the right: the PATH of file: may hold colons
             head, sep, last = body.rpartition(":")
-            name, eq, value = last.partition("=")
-            key = {"minbins": "min_bins", "events": "capacity"}.get(name.lower())
-            if not sep or not eq or key is None:
+            name, eq, _ = last.partition("=")
+            if not sep or not eq or name.lower() not in names:
                 break
-            if key in seen:
-                raise ValueError(text)
-            seen.add(key)
-            spec[key] = int(value)
             body = head
+            opts.append(last)
+        _options(opts, spec, names)
         kind, _, rest = body.partition(":")
         spec["kind"] = kind = kind.lower()
         if kind == "flat":
@@ -339,13 +356,8 @@ def _handle_mask(d):
             raise ValueError(text)
     except ValueError:
         refuse()
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: mask [{}] is ignored when playing saved spectra".format(text))
+    if _gate(d, "mask", text, "it checks the engine's own dB rows"):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: mask [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
-    if d["bUsePSD"]:
-        prg_quit(d, "ERROR:handle_args: mask [{}] needs bUsePSD false: it checks the engine's own dB rows".format(text))
     if kind == "file":
         try:
             a = np.asarray(np.load(spec["path"], allow_pickle=False), dtype=np.float32)
@@ -371,8 +383,7 @@ def _handle_zoom(d):
     """zoom D[:offsetHz[:tapsPerPhase]] (additive, zeroSpan only): the digital down-converter in front of the engine.
     d['zoom.spec'] = dict(decim, offset, taps_per_phase, ntaps, block_len, center, span), or None when the key is off; startFreq
     and endFreq become those of the zoomed span."""
-    d["zoom.spec"] = None
-    text = d["zoom"]
+    text = _key_text(d, "zoom", "zoom.spec")
     if not text:
         return
     try:
@@ -386,18 +397,13 @@ def _handle_zoom(d):
                 and 1 <= tpp <= 16 and decim * tpp <= MAX_TAPS):
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: zoom [{}]: {}".format(text, ZOOM_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: zoom [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "zoom", text, ZOOM_RULE)
+    if _gate(d, "zoom", text, "the PSD diagnostic sees the whole band"):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: zoom [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
-    if d["bUsePSD"]:
-        prg_quit(d, "ERROR:handle_args: zoom [{}] needs bUsePSD false: the PSD diagnostic sees the whole band".format(text))
     ntaps = decim * tpp
     block_len = decim * (d["fullSize"] - 1) + ntaps
     if d["frameBatch"] * block_len > MAX_IN:
-        prg_quit(d, "ERROR:handle_args: zoom [{}]: {}".format(text, ZOOM_RULE))
+        _refuse(d, "zoom", text, ZOOM_RULE)
     center, span = d["centerFreq"] + offset, d["samplingRate"] / decim
     d["zoom.spec"] = dict(decim=decim, offset=offset, taps_per_phase=tpp, ntaps=ntaps, block_len=block_len, center=center, span=span)
     d["startFreq"], d["endFreq"] = center - span / 2, center + span / 2
@@ -413,11 +419,8 @@ def _handle_channels(d):
     """channels M[:O[:tapsPerBranch[:pick]]] (additive, zeroSpan only, instead of zoom): the polyphase channelizer in front of
     the engine.  d['chan.spec'] = dict(nchan, oversample, taps_per_branch, pick, decim, ntaps, first, block_len, offset, center,
     span), or None when the key is off; startFreq and endFreq become those of the picked channel."""
-    d["chan.spec"] = None
-    text = d["channels"]
+    text = _key_text(d, "channels", "chan.spec", "channelsSave")
     if not text:
-        if d["channelsSave"]:
-            print("WARN:handle_args: channelsSave [{}] is ignored without channels".format(d["channelsSave"]))
         return
     try:
         parts = text.split(":")
@@ -431,14 +434,9 @@ def _handle_channels(d):
                 and 1 <= tpb <= _chan.MAX_BRANCH_TAPS and nchan * tpb <= _chan.MAX_TAPS and 0 <= pick < nchan):
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: channels [{}]: {}".format(text, CHANNELS_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: channels [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "channels", text, CHANNELS_RULE)
+    if _gate(d, "channels", text, "the PSD diagnostic sees the whole band"):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: channels [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
-    if d["bUsePSD"]:
-        prg_quit(d, "ERROR:handle_args: channels [{}] needs bUsePSD false: the PSD diagnostic sees the whole band".format(text))
     if d["zoom.spec"] is not None:
         prg_quit(d, "ERROR:handle_args: channels [{}] and zoom [{}] exclude each other: either is the front end of the engine".format(
             text, d["zoom"]))
@@ -446,7 +444,7 @@ def _handle_channels(d):
     first = -(-(ntaps - 1) // decim)
     block_len = decim * (first + d["fullSize"] - 1) + 1
     if d["frameBatch"] * block_len > _chan.MAX_IN:
-        prg_quit(d, "ERROR:handle_args: channels [{}]: {}".format(text, CHANNELS_RULE))
+        _refuse(d, "channels", text, CHANNELS_RULE)
     offset = float(channel_freqs(nchan, d["samplingRate"])[pick])
     center, span = d["centerFreq"] + offset, d["samplingRate"] / decim
     d["chan.spec"] = dict(nchan=nchan, oversample=over, taps_per_branch=tpb, pick=pick, decim=decim, ntaps=ntaps, first=first,
@@ -463,11 +461,8 @@ DETECT_RULE = ("detect wants T:G:THR with integers 1 <= T <= %d training and 0 <
 def _handle_detect(d):
     """detect T:G:THR[:mode=ca|go|so][:minWidth=W][:maxGap=K][:events=E] (additive, zeroSpan only): d['detect.spec'] =
     dict(train, guard, threshold, mode, min_width, max_gap, capacity), or None when the key is off."""
-    d["detect.spec"] = None
-    text = d["detect"]
+    text = _key_text(d, "detect", "detect.spec", "detectSave")
     if not text:
-        if d["detectSave"]:
-            print("WARN:handle_args: detectSave [{}] is ignored without detect".format(d["detectSave"]))
         return
     n = d["fftSize"]
     spec = dict(train=0, guard=0, threshold=0.0, mode="ca", min_width=1, max_gap=0, capacity=4096)
@@ -476,28 +471,16 @@ def _handle_detect(d):
         if len(parts) < 3:
             raise ValueError(text)
         spec["train"], spec["guard"], spec["threshold"] = int(parts[0]), int(parts[1]), float(parts[2])
-        seen = set()
-        for part in parts[3:]:                       # the optional suffixes, in any order, each at most once
-            name, eq, value = part.partition("=")
-            key = {"mode": "mode", "minwidth": "min_width", "maxgap": "max_gap", "events": "capacity"}.get(name.lower())
-            if not eq or key is None or key in seen:
-                raise ValueError(text)
-            seen.add(key)
-            spec[key] = value.lower() if key == "mode" else int(value)
+        _options(parts[3:], spec, {"mode": "mode", "minwidth": "min_width", "maxgap": "max_gap", "events": "capacity"})
         if not (1 <= spec["train"] <= _detect.MAX_TRAIN and 0 <= spec["guard"] <= _detect.MAX_GUARD
                 and np.isfinite(spec["threshold"]) and 0 <= spec["threshold"] <= 100 and spec["mode"] in _detect.MODES
                 and 1 <= spec["min_width"] <= n and 0 <= spec["max_gap"] <= _detect.MAX_GAP
                 and 1 <= spec["capacity"] <= _detect.MAX_CAPACITY and _detect.MIN_NBINS <= n <= _detect.MAX_NBINS):
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: detect [{}]: {}".format(text, DETECT_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: detect [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "detect", text, DETECT_RULE)
+    if _gate(d, "detect", text, "it reads the engine's own dB rows"):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: detect [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
-    if d["bUsePSD"]:
-        prg_quit(d, "ERROR:handle_args: detect [{}] needs bUsePSD false: it reads the engine's own dB rows".format(text))
     d["detect.spec"] = spec
 
 
@@ -509,11 +492,8 @@ TRACK_RULE = ("track wants GAP:SLOP with integers 0 <= GAP <= %d missing frames 
 def _handle_track(d):
     """track GAP:SLOP[:minRows=R][:minSpans=S][:events=E] (additive, zeroSpan only, needs detect): d['track.spec'] =
     dict(row_gap, bin_slop, min_rows, min_spans, capacity), or None when the key is off."""
-    d["track.spec"] = None
-    text = d["track"]
+    text = _key_text(d, "track", "track.spec", "trackSave")
     if not text:
-        if d["trackSave"]:
-            print("WARN:handle_args: trackSave [{}] is ignored without track".format(d["trackSave"]))
         return
     spec = dict(row_gap=0, bin_slop=0, min_rows=1, min_spans=1, capacity=4096)
     try:
@@ -521,25 +501,15 @@ def _handle_track(d):
         if len(parts) < 2:
             raise ValueError(text)
         spec["row_gap"], spec["bin_slop"] = int(parts[0]), int(parts[1])
-        seen = set()
-        for part in parts[2:]:                       # the optional suffixes, in any order, each at most once
-            name, eq, value = part.partition("=")
-            key = {"minrows": "min_rows", "minspans": "min_spans", "events": "capacity"}.get(name.lower())
-            if not eq or key is None or key in seen:
-                raise ValueError(text)
-            seen.add(key)
-            spec[key] = int(value)
+        _options(parts[2:], spec, {"minrows": "min_rows", "minspans": "min_spans", "events": "capacity"})
         if not (0 <= spec["row_gap"] <= _track.MAX_ROW_GAP and 0 <= spec["bin_slop"] <= d["fftSize"]
                 and 1 <= spec["min_rows"] < 2 ** 31 and 1 <= spec["min_spans"] < 2 ** 31
                 and 1 <= spec["capacity"] <= _track.MAX_CAPACITY):
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: track [{}]: {}".format(text, TRACK_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: track [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "track", text, TRACK_RULE)
+    if _gate(d, "track", text):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: track [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
     if d["detect.spec"] is None:
         prg_quit(d, "ERROR:handle_args: track [{}] links the emissions of detect: give [detect T:G:THR] as well".format(text))
     d["track.spec"] = spec
@@ -555,11 +525,8 @@ CORR_FILE_RULE = ("a complex template [K] or bank [Q][K] with 1 <= K <= %d, 1 <=
 def _handle_correlate(d):
     """correlate FILE.npy[:threshold[:guard[:events=N]]] (additive, zeroSpan only): d['corr.spec'] = dict(file, templates,
     threshold, guard, capacity), or None when the key is off."""
-    d["corr.spec"] = None
-    text = d["correlate"]
+    text = _key_text(d, "correlate", "corr.spec", "correlateSave")
     if not text:
-        if d["correlateSave"]:
-            print("WARN:handle_args: correlateSave [{}] is ignored without correlate".format(d["correlateSave"]))
         return
     spec = dict(file="", templates=None, threshold=0.5, guard=None, capacity=4096)
     try:
@@ -571,16 +538,12 @@ def _handle_correlate(d):
             spec["threshold"] = float(parts[1])
         if len(parts) > 2:
             spec["guard"] = int(parts[2])
-        if len(parts) > 3:
-            name, eq, value = parts[3].partition("=")
-            if not eq or name.lower() != "events":
-                raise ValueError(text)
-            spec["capacity"] = int(value)
+        _options(parts[3:], spec, {"events": "capacity"})
         if not (np.isfinite(spec["threshold"]) and 0 < spec["threshold"] <= 1 and 1 <= spec["capacity"] <= _corr.MAX_CAPACITY
                 and (spec["guard"] is None or 1 <= spec["guard"] <= _corr.MAX_GUARD)):
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: correlate [{}]: {}".format(text, CORR_RULE))
+        _refuse(d, "correlate", text, CORR_RULE)
     try:
         t = np.load(spec["file"], allow_pickle=False)
         if not (isinstance(t, np.ndarray) and np.iscomplexobj(t) and t.ndim in (1, 2)):
@@ -595,11 +558,8 @@ def _handle_correlate(d):
     spec["templates"] = t
     if spec["guard"] is None:
         spec["guard"] = k
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: correlate [{}] is ignored when playing saved spectra".format(text))
+    if _gate(d, "correlate", text):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: correlate [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
     if d["zoom"] or d["channels"]:
         prg_quit(d, "ERROR:handle_args: correlate [{}] reads the raw blocks: correlating behind zoom or channels is out of scope, "
                     "drop [{}]".format(text, "zoom" if d["zoom"] else "channels"))
@@ -618,11 +578,8 @@ PULSE_RULE = ("pulses wants [rel:]ON_DB:OFF_DB[:W[:minLen[:events=N]]] with fini
 def _handle_pulses(d):
     """pulses [rel:]ON_DB:OFF_DB[:W[:minLen[:events=N]]] (additive, zeroSpan only): d['pulse.spec'] = dict(rel, on_db, off_db,
     W, min_len, capacity), or None when the key is off."""
-    d["pulse.spec"] = None
-    text = d["pulses"]
+    text = _key_text(d, "pulses", "pulse.spec", "pulsesSave")
     if not text:
-        if d["pulsesSave"]:
-            print("WARN:handle_args: pulsesSave [{}] is ignored without pulses".format(d["pulsesSave"]))
         return
     spec = dict(rel=False, on_db=0.0, off_db=0.0, W=16, min_len=1, capacity=1024)
     try:
@@ -637,11 +594,7 @@ def _handle_pulses(d):
             spec["W"] = int(parts[2])
         if len(parts) > 3:
             spec["min_len"] = int(parts[3])
-        if len(parts) > 4:
-            name, eq, value = parts[4].partition("=")
-            if not eq or name.lower() != "events":
-                raise ValueError(text)
-            spec["capacity"] = int(value)
+        _options(parts[4:], spec, {"events": "capacity"})
         if not (np.isfinite(spec["on_db"]) and np.isfinite(spec["off_db"]) and spec["off_db"] <= spec["on_db"]
                 and 1 <= spec["W"] <= _pulse.MAX_W and 1 <= spec["min_len"] <= _pulse.MAX_MIN_LEN
                 and 1 <= spec["capacity"] <= _pulse.MAX_CAPACITY):
@@ -651,12 +604,9 @@ def _handle_pulses(d):
             if not (0 < off <= on <= 4 and round(off * _pulse.POWER_UNIT * spec["W"]) >= 1):
                 raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: pulses [{}]: {}".format(text, PULSE_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: pulses [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "pulses", text, PULSE_RULE)
+    if _gate(d, "pulses", text):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: pulses [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
     if d["zoom"] or d["channels"]:
         prg_quit(d, "ERROR:handle_args: pulses [{}] reads the raw blocks: detecting pulses behind zoom or channels is out of scope, "
                     "drop [{}]".format(text, "zoom" if d["zoom"] else "channels"))
@@ -671,11 +621,8 @@ IQFIX_RULE = ("iqfix wants MODE[:blocks=N][:track] with MODE dc|iq|dc+iq, an int
 def _handle_iqfix(d):
     """iqfix MODE[:blocks=N][:track] (additive, zeroSpan only): d['iqfix.spec'] = dict(mode, blocks, track), or None when the
     key is off; mode is the library's bits and blocks is None for all of the first batch."""
-    d["iqfix.spec"] = None
-    text = d["iqfix"]
+    text = _key_text(d, "iqfix", "iqfix.spec", "iqfixSave")
     if not text:
-        if d["iqfixSave"]:
-            print("WARN:handle_args: iqfixSave [{}] is ignored without iqfix".format(d["iqfixSave"]))
         return
     spec = dict(mode=0, blocks=None, track=False)
     try:
@@ -696,14 +643,9 @@ def _handle_iqfix(d):
         if spec["track"] and spec["blocks"] is not None:
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: iqfix [{}]: {}".format(text, IQFIX_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: iqfix [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "iqfix", text, IQFIX_RULE)
+    if _gate(d, "iqfix", text, "the PSD diagnostic reads the raw block"):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: iqfix [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
-    if d["bUsePSD"]:
-        prg_quit(d, "ERROR:handle_args: iqfix [{}] needs bUsePSD false: the PSD diagnostic reads the raw block".format(text))
     for other in ("channels", "correlate", "pulses"):
         if d[other]:
             prg_quit(d, "ERROR:handle_args: iqfix [{}] corrects the blocks the engine and zoom read: {} [{}] reads the raw blocks, "
@@ -725,11 +667,8 @@ DEMOD_RULE = ("demod wants MODE[:audioDecim[:tapsPerPhase[:deemphUs]]] with MODE
 def _handle_demod(d):
     """demod MODE[:audioDecim[:tapsPerPhase[:deemphUs]]] (additive, zeroSpan only, behind zoom): d['demod.spec'] =
     dict(mode, decim, taps_per_phase, ntaps, deemph_us, out_per_block, rate), or None when the key is off."""
-    d["demod.spec"] = None
-    text = d["demod"]
+    text = _key_text(d, "demod", "demod.spec", "demodSave")
     if not text:
-        if d["demodSave"]:
-            print("WARN:handle_args: demodSave [{}] is ignored without demod".format(d["demodSave"]))
         return
     try:
         parts = text.split(":")
@@ -743,19 +682,14 @@ def _handle_demod(d):
                 and (deemph is None or (np.isfinite(deemph) and deemph > 0))):
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: demod [{}]: {}".format(text, DEMOD_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: demod [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "demod", text, DEMOD_RULE)
+    if _gate(d, "demod", text, "the PSD diagnostic sees the whole band"):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: demod [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
-    if d["bUsePSD"]:
-        prg_quit(d, "ERROR:handle_args: demod [{}] needs bUsePSD false: the PSD diagnostic sees the whole band".format(text))
     ntaps = decim * tpp
     lead = 1 if mode == "fm" else 0
     front = d["zoom.spec"] if d["zoom.spec"] is not None else d["chan.spec"]       # channels stands in for zoom
     if front is None or d["fullSize"] < ntaps + lead:
-        prg_quit(d, "ERROR:handle_args: demod [{}]: {}".format(text, DEMOD_RULE))
+        _refuse(d, "demod", text, DEMOD_RULE)
     exact = d["samplingRate"] / (front["decim"] * decim)
     rate = int(round(exact))
     if rate != exact:
@@ -773,8 +707,7 @@ RESAMPLE_RULE = ("audioRate wants HZ[:tapsPerPhase] with a whole HZ >= 1 and an 
 def _handle_resample(d):
     """audioRate HZ[:tapsPerPhase] (additive, zeroSpan only, behind demod): d['resample.spec'] = dict(rate, rate_in, L, M,
     taps_per_phase, phase_taps, in_per_block, out_per_block), or None when the key is off."""
-    d["resample.spec"] = None
-    text = d["audioRate"]
+    text = _key_text(d, "audioRate", "resample.spec")
     if not text:
         return
     try:
@@ -786,12 +719,9 @@ def _handle_resample(d):
         if not (np.isfinite(hz) and hz >= 1 and hz == int(hz) and tpp >= 1):
             raise ValueError(text)
     except ValueError:
-        prg_quit(d, "ERROR:handle_args: audioRate [{}]: {}".format(text, RESAMPLE_RULE))
-    if d["prgMode"] == "ZEROSPANPLAY":
-        print("WARN:handle_args: audioRate [{}] is ignored when playing saved spectra".format(text))
+        _refuse(d, "audioRate", text, RESAMPLE_RULE)
+    if _gate(d, "audioRate", text):
         return
-    if d["prgMode"] != "ZEROSPAN":
-        prg_quit(d, "ERROR:handle_args: audioRate [{}] is zeroSpan only, prgMode is [{}]".format(text, d["prgMode"]))
     dspec = d["demod.spec"]
     if dspec is None:
         prg_quit(d, "ERROR:handle_args: audioRate [{}] needs demod: {}".format(text, RESAMPLE_RULE))
@@ -803,7 +733,7 @@ def _handle_resample(d):
         prg_quit(d, "ERROR:handle_args: audioRate [{}]: {}: {}".format(text, e, RESAMPLE_RULE))
     per_block = -(-dspec["out_per_block"] * L // M) - -(-(P - 1) * L // M)
     if per_block < 1:
-        prg_quit(d, "ERROR:handle_args: audioRate [{}]: {}".format(text, RESAMPLE_RULE))
+        _refuse(d, "audioRate", text, RESAMPLE_RULE)
     d["resample.spec"] = dict(rate=int(hz), rate_in=dspec["rate"], L=L, M=M, taps_per_phase=tpp, phase_taps=P,
                               in_per_block=dspec["out_per_block"], out_per_block=per_block)
 
@@ -837,6 +767,11 @@ def _handle_pfb(d):
         print("WARN:handle_args: curScanNonOverlap [{}] and curScanCumuMode [{}] are unused with pfbTaps [{}]".format(
             d["curScanNonOverlap"], d["curScanCumuMode"], taps))
     d["fullSize"] = (taps + max(1, spectra) - 1) * d["fftSize"]
+
+
+# in the order handle_args calls them: a handler reads the specs of the ones before it (channels zoom's, demod either's, ...)
+_HANDLERS = (_handle_pfb, _handle_density, _handle_mask, _handle_zoom, _handle_channels, _handle_detect, _handle_demod,
+             _handle_resample, _handle_correlate, _handle_pulses, _handle_track, _handle_iqfix)
 
 
 def print_info(d):
@@ -1302,96 +1237,95 @@ def _plot_heatmap(d, hm):
 # ------------------------------------------------------------------------------------------ zeroSpan
 def zero_span(d):
     """K:426-505.  Per frame: capture, curscan + LogNoGain + Max/Min/Avg/Cur + waterfall row on the GPU,
-    then the hand-off arrays are refreshed for the plots."""
+    then the hand-off arrays are refreshed for the plots.  Every additive key that is on is a stage (_STAGES) beside that."""
     for k in ("Fft.Max", "Fft.Min", "Fft.Avg", "Fft.Cur"):
         d[k] = None
     d["timeWasStr"] = None
     if d.get("sdr") is not None:
         d["sdr"], _ = sdr_setup(d["sdr"], d["centerFreq"], d["samplingRate"], d["gain"])
-    zoom = d.get("zoom.spec") if sdr_curscan is _gpu_curscan else None
-    cspec = d.get("chan.spec") if sdr_curscan is _gpu_curscan else None
-    front = zoom if zoom is not None else cspec  # either front end: the decimated rate around its centre
-    if front is not None:                        # the zoomed span: the decimated rate around the mixer's frequency
-        freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], front["decim"] / d["samplingRate"]) + front["center"])
-    else:
+    fused = sdr_curscan is _gpu_curscan          # not playback: only then are there blocks for the stages and for batches
+    specs = {key: d.get(key) for key, _ in _STAGES} if fused else {}
+    front = specs.get("zoom.spec") or specs.get("chan.spec")     # either front end: the decimated rate around its centre
+    if front is None:
+        specs.pop("demod.spec", None)            # the demodulator reads a front end's blocks
         freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], 1 / d["samplingRate"]) + d["centerFreq"])   # K:444-445
+    else:                                        # the zoomed span: the decimated rate around the mixer's frequency
+        freqs = np.fft.fftshift(np.fft.fftfreq(d["fftSize"], front["decim"] / d["samplingRate"]) + front["center"])
     d["freqs"] = freqs
     print("ZeroSpan: min[{}] max[{}]".format(min(freqs), max(freqs)))
     batch = d["frameBatch"]
-    if batch > 1 and sdr_curscan is not _gpu_curscan:
+    if batch > 1 and not fused:
         print("WARN:zero_span: frameBatch [{}] is ignored when playing saved spectra".format(batch))
         batch = 1
     eng = get_engine(d, max_frames=batch)
     eng.reset()
     d["fftHM"], d["fftHMIndex"] = np.zeros((_engine.HM_ROWS, eng.hm_width)), 0     # K:456; the device ring starts the same
-    spec = d.get("density.spec") if sdr_curscan is _gpu_curscan else None
-    dens = None
-    if spec is not None:                         # its columns are the waterfall's
-        dens = SpectrumDensity(d["fftSize"], eng.hm_width, spec[0], spec[1], spec[2], device=d["device"])
-    mspec = d.get("mask.spec") if sdr_curscan is _gpu_curscan else None
-    trig = _MaskFeed(d, mspec) if mspec is not None else None
-    dspec = d.get("detect.spec") if sdr_curscan is _gpu_curscan else None
-    det = _DetectFeed(d, dspec) if dspec is not None else None
-    aspec = d.get("demod.spec") if front is not None else None
-    audio = _DemodFeed(d, aspec, front, batch) if aspec is not None else None
-    bank = _ChanFeed(d, cspec, batch) if cspec is not None else None
-    kspec = d.get("corr.spec") if sdr_curscan is _gpu_curscan else None
-    corr = _CorrFeed(d, kspec, batch) if kspec is not None else None
-    pspec = d.get("pulse.spec") if sdr_curscan is _gpu_curscan else None
-    puls = _PulseFeed(d, pspec, batch) if pspec is not None else None
-    qspec = d.get("iqfix.spec") if sdr_curscan is _gpu_curscan else None
-    fix = _IqFeed(d, qspec, batch, zoom["block_len"] if zoom is not None else d["fullSize"]) if qspec is not None else None
+    raw = raw_format(d) if fused else False
+    run = _Run(batch, front["block_len"] if front is not None else d["fullSize"], raw, _raw_fmt(raw), front, freqs)
+    stages = []                                  # in the order of _STAGES, which is the order of the hand-off
     try:
-        if (batch > 1 or dens is not None or trig is not None or front is not None or det is not None or corr is not None
-                or puls is not None or fix is not None):    # density, mask, zoom, detect, correlate, pulses and iqfix run the batch route: frameBatch 1 is a batch of one
-            _zero_span_batches(d, eng, freqs, batch, dens, trig, zoom, det, audio, bank, corr, puls, fix=fix)
+        for key, cls in _STAGES:
+            if specs.get(key) is not None:
+                stages.append(cls(d, specs[key], run))
+        if stages or batch > 1:                  # every stage runs the batch route: frameBatch 1 is a batch of one
+            _zero_span_batches(d, eng, run, stages)
         else:
             _zero_span_frames(d, eng, freqs)
-        if dens is not None:
-            _density_handoff(d, dens)
-        if trig is not None:
-            trig.handoff(d)
-        if det is not None:
-            det.handoff(d, freqs)
-            if d.get("track.spec") is not None:  # one row is one frame: fullSize samples at the rate the engine was fed
-                det.link(d, freqs, d["fullSize"] * (front["decim"] if front is not None else 1) / d["samplingRate"])
-        if audio is not None:
-            audio.handoff(d)
-        if bank is not None:
-            bank.handoff(d)
-        if corr is not None:
-            corr.handoff(d)
-        if puls is not None:
-            puls.handoff(d)
-        if fix is not None:
-            fix.handoff(d)
+        for stage in stages:
+            stage.handoff(d)
     finally:
-        if fix is not None:
-            fix.close()
-        if puls is not None:
-            puls.close()
-        if corr is not None:
-            corr.close()
-        if audio is not None:
-            audio.close()
-        if bank is not None:
-            bank.close()
-        if dens is not None:
-            dens.close()
-        if trig is not None:
-            trig.close()
-        if det is not None:
-            det.close()
+        for stage in reversed(stages):           # every object owns its buffers and its destroy drains the stream first
+            stage.close()
     if _materialize(d, eng)["frames"] == 0:      # full-width arrays once, for SaveSigLvls and whoever called main()
         for k in ("Fft.Max", "Fft.Min", "Fft.Avg", "Fft.Cur"):
             d[k] = None                          # no frame ran: the curves are still None (K:427-430)
+
+
+_Run = collections.namedtuple("_Run", "batch block_len raw fmt front freqs")
+_Run.__doc__ = """What zero_span tells every stage about the run: the batch size, the samples of one raw block, what sdr_read's `raw`
+wants and the FMT_* of such blocks, the spec of the front end (zoom or channels) or None, and the frequency axis."""
+
+
+def _raw_fmt(raw):
+    """The FMT_* of the blocks sdr_read(..., raw) returns."""
+    return {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw]
+
+
+# A stage is the state of one additive key over a zeroSpan run: __init__(d, spec, run), one feeding method whose name tells
+# _zero_span_batches where it stands (feed_raw | front | feed | feed_rows), handoff(d) and close().
+class _DensityFeed:
+    """The density key's state over a run: the SpectrumDensity, fed every batch's dB rows; its columns are the waterfall's."""
+
+    def __init__(self, d, spec, run):
+        self.dens = SpectrumDensity(d["fftSize"], d["ksa.engine"].hm_width, spec[0], spec[1], spec[2], device=d["device"])
+
+    def feed_rows(self, db):
+        self.dens.add_rows(db)
+
+    def handoff(self, d):
+        """The density's hand-off arrays (drawing the bitmap is the caller's: density.image), the INFO line, densitySave."""
+        dens = self.dens
+        counts, rows = dens.read()
+        levels = dens.levels
+        d["density"], d["densityNaN"] = counts[:levels], counts[levels]
+        d["densityEdges"], d["densityRows"] = dens.level_edges(), rows
+        total = int(counts.sum())
+        clamped = int(counts[0].sum()) + (int(counts[levels - 1].sum()) if levels > 1 else 0)
+        print("INFO:zero_span: density rows [{}], levels [{}] x columns [{}], share of counts in the two clamped levels [{:.6f}]".format(
+            rows, levels, dens.width, clamped / total if total else 0.0))
+        if d["densitySave"]:
+            with open(d["densitySave"], "wb") as f:
+                np.save(f, counts)                   # [L+1, W] int64, the NaN row last
+
+    def close(self):
+        self.dens.close()
 
 
 class _MaskFeed:
     """The mask key's state over a run: the SpectrumMask (made at once for flat / file, after the first F frames for learn),
     the rows being learnt from, and the dB spectra of the stored events, picked from each batch's rows as the events arrive."""
 
-    def __init__(self, d, spec):
+    def __init__(self, d, spec, run):
         self.spec, self.n, self.device = spec, d["fftSize"], d["device"]
         self.mask, self.learnt, self.frames_done = None, [], 0
         self.event_rows, self.stored = [], 0
@@ -1402,7 +1336,7 @@ class _MaskFeed:
         self.mask = SpectrumMask(self.n, upper, lower, min_bins=self.spec["min_bins"], capacity=self.spec["capacity"],
                                  device=self.device)
 
-    def feed(self, db):
+    def feed_rows(self, db):
         """db: float32 [k][fftSize], the dB rows of frames frames_done .. frames_done + k of the run."""
         first = self.frames_done
         self.frames_done += len(db)
@@ -1458,19 +1392,21 @@ class _MaskFeed:
 class _DetectFeed:
     """The detect key's state over a run: the SignalDetector, fed every batch's dB rows; row numbers are frame numbers."""
 
-    def __init__(self, d, spec):
-        self.spec = spec
+    def __init__(self, d, spec, run):
+        self.spec, self.freqs = spec, run.freqs
+        # one row is one frame: fullSize samples at the rate the engine was fed
+        self.row_period_s = d["fullSize"] * (run.front["decim"] if run.front is not None else 1) / d["samplingRate"]
         self.det = SignalDetector(d["fftSize"], spec["train"], spec["guard"], spec["threshold"], mode=spec["mode"],
                                   min_width=spec["min_width"], max_gap=spec["max_gap"], capacity=spec["capacity"],
                                   device=d["device"])
 
-    def feed(self, db):
+    def feed_rows(self, db):
         """db: float32 [k][fftSize], the dB rows of the run's next k frames."""
         if len(db):
             self.det.detect_rows(db)
 
-    def handoff(self, d, freqs):
-        """The hand-off arrays, the INFO line, detectSave."""
+    def handoff(self, d):
+        """The hand-off arrays, the INFO line, detectSave; then, with the track key, the link over these emissions."""
         ev, total = self.det.emissions()
         hits, rows = self.det.hits()
         occ = self.det.occupancy()
@@ -1479,18 +1415,20 @@ class _DetectFeed:
         print("INFO:zero_span: detect rows [{}], emissions stored [{}] / total [{}], highest occupancy [{:.6f}] at bin [{}]".format(
             rows, len(ev), total, float(occ[busiest]), busiest))
         if d["detectSave"]:
-            center, width = emission_freqs(ev, freqs)
+            center, width = emission_freqs(ev, self.freqs)
             s = self.spec
             with open(d["detectSave"], "wb") as f:
                 np.savez(f, emissions=ev, emissions_total=np.int64(total), hits=hits, rows_seen=np.int64(rows),
                          train=np.int32(s["train"]), guard=np.int32(s["guard"]), threshold_db=np.float32(s["threshold"]),
                          mode=np.array(s["mode"]), min_width=np.int32(s["min_width"]), max_gap=np.int32(s["max_gap"]),
                          center_hz=center, width_hz=width)
+        if d.get("track.spec") is not None:
+            self.link(d)
 
-    def link(self, d, freqs, row_period_s):
+    def link(self, d):
         """The track key: one link over the detector's whole buffer where it lies; the hand-off arrays, the INFO line,
         trackSave."""
-        s = d["track.spec"]
+        s, freqs, row_period_s = d["track.spec"], self.freqs, self.row_period_s
         trk = EmissionTracker(d["fftSize"], row_gap=s["row_gap"], bin_slop=s["bin_slop"], min_rows=s["min_rows"],
                               min_spans=s["min_spans"], capacity=s["capacity"], max_spans=self.det.capacity, device=d["device"])
         try:
@@ -1514,29 +1452,34 @@ class _DetectFeed:
         self.det.close()
 
 
+def _gather_events(feed, obj, got):
+    """What _CorrFeed and _PulseFeed do after a batch of `got` blocks went to their object: the events that are new are kept
+    with `block` counted over the run, not over the batch; where the object's list is full there is nothing to fetch."""
+    if feed.stored < obj.capacity:
+        ev = obj.events()[0]                         # synchronises: the buffer is free for the next batch
+        new = ev[feed.stored:]
+        new["block"] += feed.blocks_done
+        feed.parts.append(new)
+        feed.stored = len(ev)
+    else:
+        obj.synchronize()
+    feed.blocks_done += got
+
+
 class _CorrFeed:
     """The correlate key's state over a run: the Correlator, whose block form runs over every batch's raw blocks in their
     iqFormat, read from the page-locked batch buffer; block numbers are frame numbers of the run."""
 
-    def __init__(self, d, spec, batch):
+    def __init__(self, d, spec, run):
         self.spec, self.full, self.rate = spec, d["fullSize"], d["samplingRate"]
-        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
         self.corr = Correlator(spec["templates"], threshold=spec["threshold"], guard=spec["guard"], capacity=spec["capacity"],
-                               max_in=batch * self.full, fmt=fmt, device=d["device"])
+                               max_in=run.batch * self.full, fmt=run.fmt, device=d["device"])
         self.blocks_done, self.stored, self.parts = 0, 0, []
 
-    def feed(self, blocks, got):
+    def feed_raw(self, blocks, got):
         """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
         self.corr.blocks_dev(blocks, got, self.full)
-        if self.stored < self.corr.capacity:
-            ev, _ = self.corr.events()               # synchronises: the buffer is free for the next batch
-            new = ev[self.stored:]
-            new["block"] += self.blocks_done
-            self.parts.append(new)
-            self.stored = len(ev)
-        else:
-            self.corr.synchronize()
-        self.blocks_done += got
+        _gather_events(self, self.corr, got)
 
     def handoff(self, d):
         """The hand-off arrays, the INFO line, correlateSave."""
@@ -1564,12 +1507,11 @@ class _PulseFeed:
     iqFormat, read from the page-locked batch buffer; block numbers are frame numbers of the run.  With rel: the levels are set
     from the median envelope of the run's first block before any block is searched."""
 
-    def __init__(self, d, spec, batch):
+    def __init__(self, d, spec, run):
         self.spec, self.full, self.rate = spec, d["fullSize"], d["samplingRate"]
-        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
         on, off = (1.0, 1.0) if spec["rel"] else (_pulse.db_to_power(spec["on_db"]), _pulse.db_to_power(spec["off_db"]))
         self.det = PulseDetector(W=spec["W"], on_power=on, off_power=off, min_len=spec["min_len"], capacity=spec["capacity"],
-                                 max_in=batch * self.full, fmt=fmt, device=d["device"])
+                                 max_in=run.batch * self.full, fmt=run.fmt, device=d["device"])
         self.floor = None                            # rel: the median of S / W over the first block, in units of 2^-30
         self.blocks_done, self.stored, self.parts = 0, 0, []
 
@@ -1586,20 +1528,12 @@ class _PulseFeed:
         base = self.floor / _pulse.POWER_UNIT
         self.det.set_params(base * 10.0 ** (self.spec["on_db"] / 10.0), base * 10.0 ** (self.spec["off_db"] / 10.0))
 
-    def feed(self, blocks, got):
+    def feed_raw(self, blocks, got):
         """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
         if self.spec["rel"] and self.floor is None:
             self._set_relative_levels(blocks)
         self.det.blocks_dev(blocks, got, self.full)
-        if self.stored < self.det.capacity:
-            ev = self.det.events()[0]                # synchronises: the buffer is free for the next batch
-            new = ev[self.stored:]
-            new["block"] += self.blocks_done
-            self.parts.append(new)
-            self.stored = len(ev)
-        else:
-            self.det.synchronize()
-        self.blocks_done += got
+        _gather_events(self, self.det, got)
 
     def handoff(self, d):
         """The hand-off arrays, the INFO line, pulsesSave."""
@@ -1628,10 +1562,9 @@ class _IqFeed:
     the first batch's first `blocks` blocks are measured and solved once, before anything runs; with track every batch is
     measured in the pass that corrects it, and what it solves to corrects the next one."""
 
-    def __init__(self, d, spec, batch, block_len):
-        self.spec, self.full = spec, block_len
-        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
-        self.fix = IqCorrector(fmt=fmt, max_in=batch * block_len, device=d["device"])
+    def __init__(self, d, spec, run):
+        self.spec, self.full = spec, run.block_len       # zoom's block length or fullSize: it never runs with channels
+        self.fix = IqCorrector(fmt=run.fmt, max_in=run.batch * run.block_len, device=d["device"])
         self.batches, self.solves = 0, []
 
     @property
@@ -1643,8 +1576,8 @@ class _IqFeed:
         sol = self.fix.solve(self.spec["mode"])
         self.solves.append((self.batches, sol, sums))
 
-    def run(self, blocks, got):
-        """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
+    def feed_raw(self, blocks, got):
+        """blocks: the batch buffer, whose first `got` rows are the run's next blocks; out_ptr is where their corrected form lies."""
         if self.spec["track"]:
             self.fix.blocks_dev(blocks, got, self.full, accumulate=True)
             self._solve()                            # synchronises; the new coefficients serve the next batch
@@ -1685,9 +1618,9 @@ class _DemodFeed:
     """The demod key's state over a run: the Demodulator behind the down-converter, fed every batch's zoomed blocks in device
     memory; each block is demodulated on its own and the blocks abut in the audio."""
 
-    def __init__(self, d, spec, zoom, batch):
-        self.spec, self.full = spec, d["fullSize"]
-        fs = d["samplingRate"] / zoom["decim"]
+    def __init__(self, d, spec, run):
+        self.spec, self.full, batch = spec, d["fullSize"], run.batch
+        fs = d["samplingRate"] / run.front["decim"]
         taps = demod_taps(spec["decim"], spec["taps_per_phase"], deemph_us=spec["deemph_us"],
                           sampling_rate=fs if spec["deemph_us"] is not None else None, dc_block=spec["mode"] == "am")
         self.rspec, self.res = d.get("resample.spec"), None
@@ -1726,18 +1659,39 @@ class _DemodFeed:
             self.res.close()
 
 
+class _ZoomFeed:
+    """The zoom key's state over a run: the DownConverter in front of the engine, fed every batch's raw blocks -- or, behind
+    iqfix, the corrector's complex64 ones; its [got][fullSize] complex64 outputs go on from its own buffer."""
+
+    def __init__(self, d, spec, run):
+        self.block_len = spec["block_len"]
+        fmt = FMT_C64 if d.get("iqfix.spec") is not None else run.fmt
+        self.ddc = DownConverter(fmt, spec["decim"], ddc_lowpass(spec["decim"], spec["taps_per_phase"]), freq=spec["offset"],
+                                 sampling_rate=d["samplingRate"], max_in=run.batch * self.block_len, device=d["device"])
+
+    def front(self, src, got):
+        """(address, no stride) of [got][fullSize] complex64; src is the batch buffer or the corrector's address."""
+        self.ddc.blocks_dev(src, got, self.block_len)
+        return self.ddc.out_ptr, None
+
+    def handoff(self, d):
+        """Nothing of its own: the zoomed span is what the engine and the other stages hand off."""
+
+    def close(self):
+        self.ddc.close()
+
+
 class _ChanFeed:
     """The channels key's state over a run: the Channelizer in front of the engine, fed every batch's raw blocks; the picked
     channel of every block goes on as a strided view of its buffer, and every channel's power is summed over the run."""
 
-    def __init__(self, d, spec, batch):
+    def __init__(self, d, spec, run):
         self.spec, self.full = spec, d["fullSize"]
-        fmt = {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[raw_format(d)]
-        self.bank = Channelizer(fmt, spec["nchan"], spec["oversample"], chan_prototype(spec["nchan"], spec["taps_per_branch"]),
-                                max_in=batch * spec["block_len"], device=d["device"])
+        self.bank = Channelizer(run.fmt, spec["nchan"], spec["oversample"], chan_prototype(spec["nchan"], spec["taps_per_branch"]),
+                                max_in=run.batch * spec["block_len"], device=d["device"])
         self.power, self.values = np.zeros(spec["nchan"], dtype=np.float64), 0
 
-    def run(self, blocks, got):
+    def front(self, blocks, got):
         """(address, stride in values) of the picked channel of every block: [got][M][fullSize] complex64 in the bank's buffer."""
         cols = self.bank.blocks_dev(blocks, got, self.spec["block_len"])
         assert cols == self.full
@@ -1763,21 +1717,6 @@ class _ChanFeed:
 
     def close(self):
         self.bank.close()
-
-
-def _density_handoff(d, dens):
-    """The density's hand-off arrays (drawing the bitmap is the caller's: density.image), the INFO line, densitySave."""
-    counts, rows = dens.read()
-    levels = dens.levels
-    d["density"], d["densityNaN"] = counts[:levels], counts[levels]
-    d["densityEdges"], d["densityRows"] = dens.level_edges(), rows
-    total = int(counts.sum())
-    clamped = int(counts[0].sum()) + (int(counts[levels - 1].sum()) if levels > 1 else 0)
-    print("INFO:zero_span: density rows [{}], levels [{}] x columns [{}], share of counts in the two clamped levels [{:.6f}]".format(
-        rows, levels, dens.width, clamped / total if total else 0.0))
-    if d["densitySave"]:
-        with open(d["densitySave"], "wb") as f:
-            np.save(f, counts)                   # [L+1, W] int64, the NaN row last
 
 
 def _zero_span_frames(d, eng, freqs):
@@ -1806,40 +1745,33 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
-def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, det=None, audio=None, bank=None, corr=None,
-                       puls=None, fix=None):
-    """frameBatch B > 1: up to B blocks are read into one page-locked batch buffer and handed over with ONE call
-    (ksa_frames_c64 / _u8; int8 / int16 blocks are read by the kernels from that buffer: ksa_frames_dev); flags, the progress
-    line and the plot refresh come once per batch.  prgLoopCnt still counts
-    frames, and a source that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of
-    frameBatch 1.  With a density object every batch also returns its frames' dB rows, which the object counts; with a mask
-    they are checked against its lines, with a detector they are searched for emissions (all may be on: they consume the same
-    rows).  With zoom every block is
-    D x (fullSize - 1) + T raw samples: the down-converter reads the batch from the page-locked buffer (kdc_blocks_dev) and the
-    engine takes its fullSize complex64 outputs per block from device memory (ksa_frames_dev), the dB rows coming back through
-    page-locked memory as on the int8 / int16 route.  With demod the demodulator's block form runs over the same zoomed blocks
-    (kdm_blocks_dev) and the batch's int16 audio is fetched with kdm_read_out.  With channels in place of zoom every block is
-    the channelizer's block length, kch_blocks_dev leaves [got][M][fullSize] complex64 in its buffer, and the engine and the
-    demodulator read the picked channel of every block at a stride of M x fullSize values.  With correlate (never together with
-    a front end) the correlator's block form reads the batch's raw blocks from the same page-locked buffer (kcr_blocks_dev), and
-    with pulses the pulse detector's block form does (kpl_blocks_dev).  With iqfix the corrector runs first: it reads the raw
-    batch from the page-locked buffer (kqf_blocks_dev) and leaves [got][block length] complex64 in its own buffer, which the
-    down-converter (then made for complex64) or the engine (ksa_frames_dev) reads instead of the raw batch."""
-    u8 = raw_format(d)                                                       # what sdr_read(..., raw) delivers
-    full = zoom["block_len"] if zoom is not None else bank.spec["block_len"] if bank is not None else d["fullSize"]
+def _zero_span_batches(d, eng, run, stages):
+    """The batch route: up to run.batch blocks are read into ONE page-locked buffer and go through the engine and the stages in
+    one pass; flags, the progress line and the plot refresh come once per batch.  prgLoopCnt still counts frames, and a source
+    that runs out mid-batch stops the run after the whole blocks it delivered: the frames are those of frameBatch 1.  Per batch,
+    in this order:
+    - the corrector (feed_raw + out_ptr: iqfix) reads the raw batch and leaves [got][block_len] complex64 in its own buffer,
+      which stands in for the batch from here to the engine;
+    - a front end (front: zoom | channels) reads that and returns (address, stride) of [got][fullSize] complex64 on the device;
+    - the engine takes those blocks from device memory (ksa_frames_dev), else the batch itself (ksa_frames_c64 / _u8; int8 /
+      int16 blocks are read by the kernels from the page-locked buffer), and returns the batch's dB rows if a row stage is on;
+    - the demodulator (feed: demod, audioRate) reads the front end's blocks and keeps the batch's int16 audio on the host;
+    - the row stages (feed_rows: density, mask, detect) read the dB rows; counts and events stay on the GPU until the hand-off;
+    - the raw stages (feed_raw: correlate, pulses) read the page-locked batch and keep the new events, block counted over the run."""
+    fix = next((s for s in stages if hasattr(s, "feed_raw") and hasattr(s, "out_ptr")), None)
+    front = next((s for s in stages if hasattr(s, "front")), None)
+    audio = next((s for s in stages if hasattr(s, "feed")), None)
+    rows = [s for s in stages if hasattr(s, "feed_rows")]
+    raws = [s for s in stages if hasattr(s, "feed_raw") and s is not fix]
+    u8, full = run.raw, run.block_len                                        # what sdr_read(..., raw) delivers
     dtype, per = raw_dtype(u8)
-    ddc = None
-    if zoom is not None:
-        fmt = FMT_C64 if fix is not None else {False: FMT_C64, True: FMT_U8, "s8": FMT_S8, "s16": FMT_S16}[u8]
-        ddc = DownConverter(fmt, zoom["decim"], ddc_lowpass(zoom["decim"], zoom["taps_per_phase"]), freq=zoom["offset"],
-                            sampling_rate=d["samplingRate"], max_in=batch * full, device=d["device"])
-    stage = _engine.PinnedBuffer((batch, per * full), dtype)
+    stage = _engine.PinnedBuffer((run.batch, per * full), dtype)
     blocks = stage.array
     read_blocks = getattr(d["sdr"], "read_blocks", None)
     try:
         done, prev = 0, time.time()
         while done < d["prgLoopCnt"]:
-            k = min(batch, d["prgLoopCnt"] - done)
+            k = min(run.batch, d["prgLoopCnt"] - done)
             now = time.time()
             print("ZeroSpan:{}:{}".format(done, now - prev))
             prev = now
@@ -1854,51 +1786,42 @@ def _zero_span_batches(d, eng, freqs, batch, dens=None, trig=None, zoom=None, de
                         got += 1
                 except EOFError:
                     pass
-            if got and fix is not None:
-                fix.run(blocks, got)                                         # [got][full] complex64 in its own buffer
-            if got and (ddc is not None or bank is not None or fix is not None):
-                if ddc is not None:
-                    ddc.blocks_dev(blocks if fix is None else fix.out_ptr, got, full)   # [got][fullSize] complex64 in its own buffer
-                    src, stride = ddc.out_ptr, None
-                elif bank is not None:
-                    src, stride = bank.run(blocks, got)                      # one channel of [got][M][fullSize]
+            if got:
+                src, stride, db = blocks, None, None
+                if fix is not None:
+                    fix.feed_raw(blocks, got)
+                    src = fix.out_ptr
+                if front is not None:
+                    src, stride = front.front(src, got)
+                if src is not blocks:                                        # [got][fullSize] complex64 in device memory
+                    if rows:
+                        db = eng._pinned_out("db", (got, d["fftSize"]))
+                    eng.frames_dev(src, FMT_C64, got, cur_db=db, frame_stride=stride)
+                    eng.synchronize()
+                    if audio is not None:
+                        audio.feed(src, got, stride)
+                elif rows:
+                    db = eng.frames(blocks[:got], cur_db=True)[0]
                 else:
-                    src, stride = fix.out_ptr, None
-                db = eng._pinned_out("db", (got, d["fftSize"])) if dens is not None or trig is not None or det is not None else None
-                eng.frames_dev(src, FMT_C64, got, cur_db=db, frame_stride=stride)
-                eng.synchronize()
-                if audio is not None:
-                    audio.feed(src, got, stride)
-                if dens is not None:
-                    dens.add_rows(db)
-                if trig is not None:
-                    trig.feed(db)
-                if det is not None:
-                    det.feed(db)
-            elif got and dens is None and trig is None and det is None:
-                eng.frames(blocks[:got])                                     # K:464-484 for the whole batch, one call
-            elif got:
-                db = eng.frames(blocks[:got], cur_db=True)[0]
-                if dens is not None:
-                    dens.add_rows(db)
-                if trig is not None:
-                    trig.feed(db)
-                if det is not None:
-                    det.feed(db)
-            if got and corr is not None:
-                corr.feed(blocks, got)
-            if got and puls is not None:
-                puls.feed(blocks, got)
+                    eng.frames(blocks[:got])                                 # K:464-484 for the whole batch, one call
+                for s in rows:
+                    s.feed_rows(db)
+                for s in raws:
+                    s.feed_raw(blocks, got)
             done += got
             if got < k:
                 prg_quit(d, "WARN:zero_span: source exhausted, stoping...", False)
             if d["cmd.stop"]:
                 break
-            _handoff(d, eng, freqs, new_rows=min(got, _engine.HM_ROWS))     # once per batch: the batch's newest rows
+            _handoff(d, eng, run.freqs, new_rows=min(got, _engine.HM_ROWS))  # once per batch: the batch's newest rows
     finally:
-        if ddc is not None:
-            ddc.close()
         stage.close()
+
+
+# spec key -> stage class, in the order of construction and of the hand-off; the row stages and the raw stages are fed in it
+_STAGES = (("density.spec", _DensityFeed), ("mask.spec", _MaskFeed), ("detect.spec", _DetectFeed), ("demod.spec", _DemodFeed),
+           ("zoom.spec", _ZoomFeed), ("chan.spec", _ChanFeed), ("corr.spec", _CorrFeed), ("pulse.spec", _PulseFeed),
+           ("iqfix.spec", _IqFeed))
 
 
 def zero_span_save(d):
