@@ -14,7 +14,8 @@ known waveform lies, in libksa_corr.so; PulseDetector (pulse.py) is the time-dom
 samples: when something was on the air, in libksa_pulse.so; EmissionTracker (track.py) is the linker behind the signal
 detector: its per-row emissions joined into time-frequency tracks, a signal list, in libksa_track.so; IqCorrector (iqfix.py)
 is the blind DC-offset and IQ-imbalance corrector in front of all of them: raw samples in, corrected complex64 out, and the
-integer sums the correction is solved from, in libksa_iqfix.so.
+integer sums the correction is solved from, in libksa_iqfix.so; ScanSurvey (survey.py) is the detector and the linker under a
+scan: the emissions of every tuned band joined over the stitched range, one list per pass, over those same libraries.
 """
 from ._lib import KsaError, lib, LIB_PATH, FMT_C64, FMT_U8, FMT_S8, FMT_S16, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS, CUMU_PFB, CUMU_PFB_PSD
 from .engine import (SpectrumEngine, PinnedBuffer, allreduce_state, scan_allstitch, scan_gather_state, full_size_for,
@@ -31,6 +32,7 @@ from .corr import Correlator, frequency_bank, refine
 from .pulse import PulseDetector, PULSE_DTYPE, FLAG_OPEN_END, POWER_UNIT
 from .track import EmissionTracker, TRACK_DTYPE, SPAN_DTYPE, track_times_freqs      # track.FLAG_OPEN_END is the same bit 0
 from .iqfix import IqCorrector, imbalance_of
+from .survey import ScanSurvey, stitch_emissions
 
 __all__ = ["KsaError", "SpectrumEngine", "lib", "LIB_PATH", "FMT_C64", "FMT_U8", "FMT_S8", "FMT_S16", "OUT_LINEAR", "OUT_DB",
            "OUT_DB_CLIP", "HM_ROWS", "PinnedBuffer", "allreduce_state", "scan_allstitch", "scan_gather_state", "full_size_for", "window_starts", "window_table", "heatmap_width",
@@ -39,4 +41,5 @@ __all__ = ["KsaError", "SpectrumEngine", "lib", "LIB_PATH", "FMT_C64", "FMT_U8",
            "SignalDetector", "EMISSION_DTYPE", "emission_freqs", "Demodulator", "demod_taps", "write_wav",
            "Channelizer", "chan_prototype", "channel_freqs", "Resampler", "resample_taps", "rate_ratio",
            "Correlator", "frequency_bank", "refine", "PulseDetector", "PULSE_DTYPE", "FLAG_OPEN_END", "POWER_UNIT",
-           "EmissionTracker", "TRACK_DTYPE", "SPAN_DTYPE", "track_times_freqs", "IqCorrector", "imbalance_of"]
+           "EmissionTracker", "TRACK_DTYPE", "SPAN_DTYPE", "track_times_freqs", "IqCorrector", "imbalance_of",
+           "ScanSurvey", "stitch_emissions"]

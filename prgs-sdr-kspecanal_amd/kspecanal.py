@@ -64,6 +64,19 @@ corrector in front of everything else -- the sums of the first N blocks of the f
 correction that every block of the run then gets before the engine (or `zoom`) sees it; with track every batch is corrected
 with the coefficients solved from the batch before it; handed off as d['iqfix'], a dict of per-solve arrays; default empty =
 off) and `iqfixSave` (an .npz of those arrays: batch, dc_i, dc_q, c, d, flags, count, sums, gain_db and phase_deg per solve).
+The scan modes have keys of their own: `scanDetect` (T:G:THR[:mode=ca|go|so][:minWidth=W][:maxGap=K][:events=E][:edge=K][:dc=K],
+scan modes only: the CFAR detector of `detect` over every tuned band's dB row of every pass -- each band has its own gain and
+floor --, the band emissions mapped to the stitched range and the sightings that overlapping bands give of one emission joined
+into one record per pass (survey.stitch_emissions); dc=K drops what lies within K bins of a band's centre, the receiver's
+spike, edge=K what peaks in the outer K bins of a band while another band sees the same frequency further inside; events is
+the room of the run's list, whose total counts every emission; handed off as d['surveyEmissions'] (row is the pass, the bins
+index d['freqsAll']), d['surveyMembers'], d['surveyEmissionsTotal'], d['surveyCounters'], d['surveyOccupancy'] (per xRes cell,
+the passes in which an emission touched it) and d['surveyPasses']; default empty = off), `scanDetectSave` (an .npz of those, the
+parameters, and every emission's centre, width and peak in Hz), `scanTrack` (GAP:SLOP[:minRows=R][:minSpans=S][:events=E], scan
+modes only, needs `scanDetect`: at the end of the run the stored emissions are linked on the GPU over the passes -- GAP in
+missing passes, SLOP in stitched bins; handed off as d['surveyTracks'], d['surveyTrackTotal'], d['surveyTrackComponents'] and
+d['surveyTrackLabels']; default empty = off) and `scanTrackSave` (an .npz like trackSave's, a row being a pass of the measured
+mean duration).
 What moved to the GPU:
 everything from the IQ block to those arrays.
 Deliberate differences: playback needs no SDR; in scan mode the Levels plot is
@@ -105,6 +118,7 @@ from . import track as _track
 from .track import EmissionTracker, track_times_freqs
 from . import iqfix as _iqfix
 from .iqfix import IqCorrector
+from .survey import ScanSurvey
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -142,6 +156,8 @@ _KEYS = {
     "PULSES": ("pulses", str), "PULSESSAVE": ("pulsesSave", str),
     "TRACK": ("track", str), "TRACKSAVE": ("trackSave", str),
     "IQFIX": ("iqfix", str.lower), "IQFIXSAVE": ("iqfixSave", str),
+    "SCANDETECT": ("scanDetect", str), "SCANDETECTSAVE": ("scanDetectSave", str),
+    "SCANTRACK": ("scanTrack", str), "SCANTRACKSAVE": ("scanTrackSave", str),
 }
 
 
@@ -161,6 +177,7 @@ def defaults():
         "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
         "audioRate": "", "correlate": "", "correlateSave": "", "pulses": "", "pulsesSave": "",
         "track": "", "trackSave": "", "iqfix": "", "iqfixSave": "",
+        "scanDetect": "", "scanDetectSave": "", "scanTrack": "", "scanTrackSave": "",
     }
 
 
@@ -769,9 +786,95 @@ def _handle_pfb(d):
     d["fullSize"] = (taps + max(1, spectra) - 1) * d["fftSize"]
 
 
+# ----------------------------------------------------------------------------------------- the additive keys of the scan modes
+def _scan_key_text(d, key, spec_key, save):
+    """_key_text for a scan-only key.  d[spec_key] exists only while the key is on: the zeroSpan keys leave a None, these leave
+    nothing, so that a command line without them fills `d` as it always did."""
+    text = _key_text(d, key, spec_key, save)
+    if not text:
+        del d[spec_key]
+    return text
+
+
+def _scan_gate(d, key, text):
+    """Where a scan-only key may run: under scan, fmScan and quickFullScan, which are all prgMode SCAN by now."""
+    if d["prgMode"] != "SCAN":
+        prg_quit(d, "ERROR:handle_args: {} [{}] is scan only, prgMode is [{}]".format(key, text, d["prgMode"]))
+
+
+SCAN_DETECT_RULE = ("scanDetect wants T:G:THR with integers 1 <= T <= %d training and 0 <= G <= %d guard cells on either side and a "
+                    "finite threshold 0 <= THR <= 100 in dB, optionally followed by :mode=ca|go|so, :minWidth=W (1..fftSize), "
+                    ":maxGap=K (0..%d), :events=E (1..%d), :edge=K and :dc=K (0..fftSize/2-1 bins each), each at most once; "
+                    "fftSize %d..%d" % (_detect.MAX_TRAIN, _detect.MAX_GUARD, _detect.MAX_GAP, _detect.MAX_CAPACITY,
+                                        _detect.MIN_NBINS, _detect.MAX_NBINS))
+
+
+def _handle_scan_detect(d):
+    """scanDetect T:G:THR[:mode=ca|go|so][:minWidth=W][:maxGap=K][:events=E][:edge=K][:dc=K] (additive, scan modes only):
+    d['survey.spec'] = dict(train, guard, threshold, mode, min_width, max_gap, capacity, edge, dc); no such entry when the key
+    is off."""
+    text = _scan_key_text(d, "scanDetect", "survey.spec", "scanDetectSave")
+    if not text:
+        return
+    n = d["fftSize"]
+    spec = dict(train=0, guard=0, threshold=0.0, mode="ca", min_width=1, max_gap=0, capacity=4096, edge=0, dc=0)
+    try:
+        parts = text.split(":")
+        if len(parts) < 3:
+            raise ValueError(text)
+        spec["train"], spec["guard"], spec["threshold"] = int(parts[0]), int(parts[1]), float(parts[2])
+        _options(parts[3:], spec, {"mode": "mode", "minwidth": "min_width", "maxgap": "max_gap", "events": "capacity",
+                                   "edge": "edge", "dc": "dc"})
+        if not (1 <= spec["train"] <= _detect.MAX_TRAIN and 0 <= spec["guard"] <= _detect.MAX_GUARD
+                and np.isfinite(spec["threshold"]) and 0 <= spec["threshold"] <= 100 and spec["mode"] in _detect.MODES
+                and 1 <= spec["min_width"] <= n and 0 <= spec["max_gap"] <= _detect.MAX_GAP
+                and 1 <= spec["capacity"] <= _detect.MAX_CAPACITY and _detect.MIN_NBINS <= n <= _detect.MAX_NBINS
+                and 0 <= spec["edge"] <= n // 2 - 1 and 0 <= spec["dc"] <= n // 2 - 1):
+            raise ValueError(text)
+    except ValueError:
+        _refuse(d, "scanDetect", text, SCAN_DETECT_RULE)
+    _scan_gate(d, "scanDetect", text)
+    d["survey.spec"] = spec
+
+
+SCAN_TRACK_RULE = ("scanTrack wants GAP:SLOP with integers 0 <= GAP <= %d missing passes and 0 <= SLOP <= %d stitched bins, optionally "
+                   "followed by :minRows=R (>= 1 passes), :minSpans=S (>= 1) and :events=E (1..%d, default 4096), each at most once"
+                   % (_track.MAX_ROW_GAP, _track.MAX_NBINS, _track.MAX_CAPACITY))
+
+
+def _handle_scan_track(d):
+    """scanTrack GAP:SLOP[:minRows=R][:minSpans=S][:events=E] (additive, scan modes only, needs scanDetect):
+    d['surveyTrack.spec'] = dict(row_gap, bin_slop, min_rows, min_spans, capacity); no such entry when the key is off."""
+    text = _scan_key_text(d, "scanTrack", "surveyTrack.spec", "scanTrackSave")
+    if not text:
+        return
+    spec = dict(row_gap=0, bin_slop=0, min_rows=1, min_spans=1, capacity=4096)
+    try:
+        parts = text.split(":")
+        if len(parts) < 2:
+            raise ValueError(text)
+        spec["row_gap"], spec["bin_slop"] = int(parts[0]), int(parts[1])
+        _options(parts[2:], spec, {"minrows": "min_rows", "minspans": "min_spans", "events": "capacity"})
+        if not (0 <= spec["row_gap"] <= _track.MAX_ROW_GAP and 0 <= spec["bin_slop"] <= _track.MAX_NBINS
+                and 1 <= spec["min_rows"] < 2 ** 31 and 1 <= spec["min_spans"] < 2 ** 31
+                and 1 <= spec["capacity"] <= _track.MAX_CAPACITY):
+            raise ValueError(text)
+    except ValueError:
+        _refuse(d, "scanTrack", text, SCAN_TRACK_RULE)
+    _scan_gate(d, "scanTrack", text)
+    if d.get("survey.spec") is None:
+        prg_quit(d, "ERROR:handle_args: scanTrack [{}] links the emissions of scanDetect: give [scanDetect T:G:THR] as well".format(text))
+    total = int((d["endFreq"] - d["startFreq"]) / d["samplingRate"]) * d["fftSize"]
+    if total > _track.MAX_NBINS:
+        prg_quit(d, "ERROR:handle_args: scanTrack [{}]: the stitched range of [{}] entries exceeds the linker's [{}] bins".format(
+            text, total, _track.MAX_NBINS))
+    d["surveyTrack.spec"] = spec
+
+
 # in the order handle_args calls them: a handler reads the specs of the ones before it (channels zoom's, demod either's, ...)
 _HANDLERS = (_handle_pfb, _handle_density, _handle_mask, _handle_zoom, _handle_channels, _handle_detect, _handle_demod,
-             _handle_resample, _handle_correlate, _handle_pulses, _handle_track, _handle_iqfix)
+             _handle_resample, _handle_correlate, _handle_pulses, _handle_track, _handle_iqfix, _handle_scan_detect,
+             _handle_scan_track)
 
 
 def print_info(d):
@@ -812,6 +915,11 @@ def print_info(d):
         r = d["resample.spec"]
         print("INFO: audioRate [{}]: [{}] Hz -> [{}] Hz by L / M = [{}] / [{}], [{}] taps per phase, [{}] samples per block".format(
             r["rate"], r["rate_in"], r["rate"], r["L"], r["M"], r["phase_taps"], r["out_per_block"]))
+    if d.get("survey.spec"):
+        v = d["survey.spec"]
+        print("INFO: scanDetect [{}]: CFAR [{}] over every tuned band, [{}] training and [{}] guard cells, [{}] dB, the sightings "
+              "of overlapping bands joined per pass; edge [{}] and dc [{}] bins".format(
+                  d["scanDetect"], v["mode"], v["train"], v["guard"], v["threshold"], v["edge"], v["dc"]))
 
 
 # ------------------------------------------------------------------------------------------ SDR seam
@@ -1906,7 +2014,11 @@ def scan_range(d):
     stage = _engine.PinnedBuffer((steps, per * d["fullSize"]), dtype)
     blocks = stage.array
     d["fftHM"], d["fftHMIndex"] = eng.hm_rows(0, _engine.HM_ROWS, scan=True), 0    # K:613-614, read once
-    prev = time.time()
+    survey, sv = None, d.get("survey.spec")
+    if sv is not None:        # scanDetect: the pass goes through the survey, which leaves the engine what eng.scan_pass leaves
+        survey = ScanSurvey(eng, steps, sv["train"], sv["guard"], sv["threshold"], mode=sv["mode"], min_width=sv["min_width"],
+                            max_gap=sv["max_gap"], capacity=sv["capacity"], edge=sv["edge"], dc=sv["dc"], cells=d["xRes"])
+    began = prev = time.time()
     for i in range(d["prgLoopCnt"]):
         if d["cmd.stop"]:
             break
@@ -1922,10 +2034,63 @@ def scan_range(d):
                 continue
             blocks[s] = sdr_read(d["sdr"], d["fullSize"], raw=u8)
         eng.set_flags(d["bDataMax"], d["bDataMin"], True)
-        eng.scan_pass(blocks, step_ok=ok)
+        if survey is None:
+            eng.scan_pass(blocks, step_ok=ok)
+        else:
+            survey.scan_pass(blocks, step_ok=ok)
         _handoff(d, eng, d["freqsAll"], scan=True)
     _materialize(d, eng, scan=True)
     stage.close()
+    if survey is not None:
+        try:
+            _survey_handoff(d, survey, time.time() - began)
+        finally:
+            survey.close()
+
+
+def _survey_handoff(d, survey, elapsed_s):
+    """The scanDetect key's hand-off arrays, the INFO line, scanDetectSave; then, with the scanTrack key, the link over the
+    passes, its hand-off arrays, INFO line and scanTrackSave.  A row of the tracker is a pass: row_period_s is the measured mean
+    time per pass."""
+    s, freqs = d["survey.spec"], d["freqsAll"]
+    ev, members, total = survey.emissions()
+    occ, passes, counters = survey.occupancy(), survey.passes, dict(survey.counters)
+    d["surveyEmissions"], d["surveyMembers"], d["surveyEmissionsTotal"] = ev, members, total
+    d["surveyCounters"], d["surveyOccupancy"], d["surveyPasses"] = counters, occ, passes
+    busiest = int(np.argmax(occ))
+    print("INFO:scan_range: survey passes [{}], emissions stored [{}] / total [{}], dropped dc [{}] edge [{}] clipped [{}], "
+          "highest occupancy [{:.6f}] at cell [{}] of [{}]".format(
+              passes, len(ev), total, counters["dc_dropped"], counters["edge_dropped"], counters["clipped"],
+              float(occ[busiest]) / passes if passes else 0.0, busiest, len(occ)))
+    if survey.band_lost:
+        print("WARN:scan_range: [{}] band emissions exceeded the detector's [{}] per pass and were not stitched".format(
+            survey.band_lost, survey.band_capacity))
+    if d["scanDetectSave"]:
+        center, width = emission_freqs(ev, freqs)
+        with open(d["scanDetectSave"], "wb") as f:
+            np.savez(f, emissions=ev, members=members, emissions_total=np.int64(total), occupancy=occ, passes=np.int64(passes),
+                     train=np.int32(s["train"]), guard=np.int32(s["guard"]), threshold_db=np.float32(s["threshold"]),
+                     mode=np.array(s["mode"]), min_width=np.int32(s["min_width"]), max_gap=np.int32(s["max_gap"]),
+                     edge=np.int32(s["edge"]), dc=np.int32(s["dc"]), center_hz=center, width_hz=width,
+                     peak_hz=np.asarray(freqs, dtype=np.float64)[ev["peak_bin"]],
+                     **{k: np.int64(v) for k, v in counters.items()})
+    t = d.get("surveyTrack.spec")
+    if t is None:
+        return
+    row_period_s = elapsed_s / passes if passes else 0.0
+    tr, tracks_total, comps, labels = survey.link(t["row_gap"], t["bin_slop"], min_rows=t["min_rows"], min_spans=t["min_spans"],
+                                                  capacity=t["capacity"])
+    d["surveyTracks"], d["surveyTrackTotal"], d["surveyTrackComponents"], d["surveyTrackLabels"] = tr, tracks_total, comps, labels
+    longest = int((tr["row_last"] - tr["row_first"] + 1).max()) if len(tr) else 0
+    print("INFO:scan_range: survey track emissions [{}], components [{}], tracks stored [{}] / total [{}], longest [{}] passes, "
+          "open at the end [{}]".format(len(labels), comps, len(tr), tracks_total, longest,
+                                        int(np.count_nonzero(tr["flags"] & _track.FLAG_OPEN_END))))
+    if d["scanTrackSave"]:
+        with open(d["scanTrackSave"], "wb") as f:
+            np.savez(f, tracks=tr, tracks_total=np.int64(tracks_total), components_total=np.int64(comps), labels=labels,
+                     row_gap=np.int32(t["row_gap"]), bin_slop=np.int32(t["bin_slop"]), min_rows=np.int32(t["min_rows"]),
+                     min_spans=np.int32(t["min_spans"]), capacity=np.int32(t["capacity"]),
+                     row_period_s=np.float64(row_period_s), **track_times_freqs(tr, freqs, row_period_s))
 
 
 # ------------------------------------------------------------------------------------------------ main
