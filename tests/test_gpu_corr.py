@@ -1,6 +1,7 @@
 """The correlator on the GPU against tests/corr_model.py (whose float32 emulation and exact generators are checked on the CPU, in
 tests/test_corr_host.py).  Shapes (K, Q) take both plans (2048 lags per workgroup, eight per thread, for Q <= 2; 1024, four per
-thread, above), K below, at and not a multiple of the lags per thread, and the limits of K and of Q K.  Lag counts sit on every
+thread, above), K below, at, one above and not a multiple of the lags per thread R ((11, 5) and (13, 6) either side of 12 at
+R = 4, (17, 2) one above 16 at R = 8), Q in {1, 2, 3, 5, 6, 8} (Q = 4 and 7: tests/test_gpu_kernel_catalogue.py), and the limits of K and of Q K.  Lag counts sit on every
 edge of the tile: 0, 1, 2, W-1, W, W+1, 3W+5, once from a pointer one sample into a 16-byte-aligned allocation, and every input
 format once.  Exact inputs are compared with np.array_equal, floats against the bound written down in corr_model."""
 import importlib
@@ -14,7 +15,7 @@ from conftest import load_pkg
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1), (2, 1), (7, 3), (64, 1), (255, 2), (256, 8), (1024, 1), (4096, 1), (2048, 8)]
+SHAPES = [(1, 1), (2, 1), (7, 3), (11, 5), (13, 6), (17, 2), (64, 1), (255, 2), (256, 8), (1024, 1), (4096, 1), (2048, 8)]
 EXACT_SHAPES = [s for s in SHAPES if s[0] <= 256]
 PLANT_SHAPES = [s for s in SHAPES if s[0] >= 64]      # below, a window of noise reaches rho 0.5 by chance (K = 1: rho is 1)
 WORST = {}

@@ -1,7 +1,8 @@
 """The digital down-converter on the GPU against tests/ddc_model.py (whose float32 emulation is checked against the bound on
 the CPU, in tests/test_ddc_host.py).  Shapes (D, T) are the smallest at which the filter takes
-each of its paths: one tap, odd and even D, every register blocking of the tile form, the large-span tile form and the reduce
-form with several chunks; output counts sit either side of a workgroup's tile (kernel_info's tile_out), which also moves the
+each of its paths: one tap, odd and even D, every register blocking of the tile form (PLANS below names each shape's: four outputs
+per thread, two -- (8, 64) and, with fewer taps than the decimation, (8, 3) --, one), the large-span tile form and the reduce
+form with several chunks; every test asserts the plan it expects from kernel_info; output counts sit either side of a workgroup's tile (kernel_info's tile_out), which also moves the
 16-byte loads of a tile over every alignment.  Impulses and integers are compared exactly, floats against the bound written
 down in ddc_model.bound."""
 import importlib
@@ -14,7 +15,11 @@ from conftest import load_pkg
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1), (1, 33), (2, 16), (3, 11), (4, 32), (5, 35), (16, 128), (64, 1024), (1024, 16384)]
+SHAPES = [(1, 1), (1, 33), (2, 16), (3, 11), (4, 32), (5, 35), (8, 64), (8, 3), (16, 128), (64, 1024), (1024, 16384)]
+# (D, T) -> (tile_out, form) of kernel_info: 256 threads x 4, 2 or 1 outputs (FORM_TILE = 0); 8 outputs in the reduce form (1).
+# Two outputs per thread where 511 D + T <= 7680 < 1023 D + T, one up to 255 D + T <= 17408, the reduce form beyond.
+PLANS = {(1, 1): (1024, 0), (1, 33): (1024, 0), (2, 16): (1024, 0), (3, 11): (1024, 0), (4, 32): (1024, 0), (5, 35): (1024, 0),
+         (8, 64): (512, 0), (8, 3): (512, 0), (16, 128): (256, 0), (64, 1024): (256, 0), (1024, 16384): (8, 1)}
 INT_SHAPES = [s for s in SHAPES if s[1] <= 64]
 FMTS = (dm.FMT_C64, dm.FMT_U8, dm.FMT_S8, dm.FMT_S16)
 INC = round(0.1234567 * 2 ** 64)
@@ -35,7 +40,9 @@ def X():
 
 
 def counts_for(dc, shape):
-    t = dc.kernel_info()["tile_out"]
+    info = dc.kernel_info()
+    assert (info["tile_out"], info["form"]) == PLANS[shape], (shape, info)
+    t = info["tile_out"]
     return [1, 3 * t + 7] if shape == SHAPES[-1] else sorted({1, max(1, t - 1), t, t + 1, 3 * t + 7})
 
 
@@ -199,6 +206,7 @@ def test_the_cut_of_the_stream_does_not_show(X, torch_cuda, shape):
     taps = lowpass(X, D, T)
     for fmt in (dm.FMT_C64, dm.FMT_U8):
         dc = X.DownConverter(fmt, D, taps, phase_inc=INC, max_in=1 << 18)
+        counts_for(dc, shape)                              # (asserts the plan)
         t = dc.kernel_info()["tile_out"]
         cuts = [1, D - 1, D, max(T - 2, 0), T - 1, T, 0]
         cuts.append(D * (2 * t + 5) + 3)

@@ -1,6 +1,6 @@
 """The demodulator on the GPU against tests/demod_model.py (whose float32 emulation is checked against the bound on the CPU, in
-tests/test_demod_host.py).  Shapes (D, T) take every tile the plan picks (1024 outputs, four per thread; 256; 64) and the
-largest span; input lengths sit on every edge of the loader and the tile: 1, 2, D-1, D, D+1, T-1, T, one tile of outputs
+tests/test_demod_host.py).  Shapes (D, T) take every tile the plan picks (1024 outputs, four per thread; 256; 64), the
+largest span and a filter with fewer taps than the decimation ((8, 3): whole input samples lie between two outputs' spans); input lengths sit on every edge of the loader and the tile: 1, 2, D-1, D, D+1, T-1, T, one tile of outputs
 +-1, three tiles + 5, and once from a pointer offset by one sample (8 mod 16).  Exact inputs are compared with
 np.array_equal, floats against the bound written down in demod_model.bound."""
 import importlib
@@ -16,8 +16,8 @@ from conftest import ROOT, load_pkg
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1), (1, 33), (2, 16), (3, 11), (5, 80), (64, 1024), (256, 4096)]
-TILES = {(1, 1): 1024, (1, 33): 1024, (2, 16): 1024, (3, 11): 1024, (5, 80): 1024, (64, 1024): 256, (256, 4096): 64}
+SHAPES = [(1, 1), (1, 33), (2, 16), (3, 11), (8, 3), (5, 80), (64, 1024), (256, 4096)]
+TILES = {(1, 1): 1024, (1, 33): 1024, (2, 16): 1024, (3, 11): 1024, (8, 3): 1024, (5, 80): 1024, (64, 1024): 256, (256, 4096): 64}
 MODES = (mm.MODE_AM, mm.MODE_FM, mm.MODE_PM)
 NAMES = {mm.MODE_AM: "am", mm.MODE_FM: "fm", mm.MODE_PM: "pm"}
 WORST = {}                                   # (D, T) -> worst error / bound of the float test, printed at the end
