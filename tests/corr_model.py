@@ -151,8 +151,7 @@ def exact_templates(rng, Q, K):
 def exact_model(x, c, min_energy=0.0):
     """Bit-exact (rho float32, r complex64): int64 sums, then one float32 division of two integers below 2^24."""
     c = _templates(c)
-    Q, K = c.shape
-    assert K <= 256
+    Q, K = c.shape                                               # K <= 256 for exact_samples; beyond, sparser samples: the asserts below
     xr, xi = np.rint(np.real(x)).astype(np.int64), np.rint(np.imag(x)).astype(np.int64)
     cr, ci = np.rint(c.real).astype(np.int64), np.rint(c.imag).astype(np.int64)
     assert np.abs(xr).max(initial=0) <= 4 and np.abs(xi).max(initial=0) <= 4 and np.all(np.abs(cr) + np.abs(ci) == 1)

@@ -28,18 +28,19 @@ PKG_DIR = os.path.join(ROOT, "prgs-sdr-kspecanal_amd")
 
 # -- the constants of the sources that the size tests mirror -------------------------------------------------------------------
 def source_constant(path, name):
-    """The integer a `constexpr <type> NAME = <expr>;` line of a source file gives; expr is integer literals, <<, * and names
-    defined the same way in the same file.  Raises when the line is not there: a constant that moved must be noticed."""
+    """The integer a `constexpr <type> NAME = <expr>;` line of a source file gives (or one declarator of such a line:
+    `constexpr int A = <expr>, NAME = <expr>;`); expr is integer literals, <<, *, / (of integers) and names defined the same way
+    in the same file.  Raises when the line is not there: a constant that moved must be noticed."""
     with open(os.path.join(PKG_DIR, path)) as f:
         text = f.read()
-    m = re.search(r"constexpr\s+(?:long long|int)\s+%s\s*=\s*([^;]+);" % re.escape(name), text)
+    m = re.search(r"constexpr\s+(?:long long|int)\s+(?:[^;]*?,\s*)?%s\s*=\s*([^;,]+)[;,]" % re.escape(name), text)
     if not m:
         raise LookupError("%s defines no constexpr %s" % (path, name))
     expr = re.sub(r"(?<=[0-9])(?:ll|LL)\b", "", m.group(1))
     expr = re.sub(r"[A-Za-z_][A-Za-z_0-9]*", lambda n: str(source_constant(path, n.group(0))), expr)
-    if not re.fullmatch(r"[0-9<*\s]+", expr):
+    if not re.fullmatch(r"[0-9<*/\s]+", expr):
         raise ValueError("%s: %s = %s is no integer expression" % (path, name, m.group(1)))
-    return int(eval(expr, {"__builtins__": {}}))                 # digits, << and * only
+    return int(eval(expr.replace("/", "//"), {"__builtins__": {}}))     # digits, <<, * and integer division only
 
 
 def mirrored_constants():
@@ -57,6 +58,24 @@ def mirrored_constants():
         "pulse.THREADS": source_constant("csrc_pulse/kpl_kernels.hpp", "THREADS"),
         "pulse.PER": source_constant("csrc_pulse/kpl_kernels.hpp", "PER"),
         "pulse.TILE": source_constant("csrc_pulse/kpl_kernels.hpp", "TILE"),
+        # the launch plans that tests/companion_sweep.py mirrors
+        "ddc.SPAN_SMALL": source_constant("csrc_ddc/kdc_api.hip", "SPAN_SMALL"),
+        "ddc.SPAN_LARGE": source_constant("csrc_ddc/kdc_api.hip", "SPAN_LARGE"),
+        "ddc.TILE_THREADS": source_constant("csrc_ddc/kdc_kernels.hpp", "TILE_THREADS"),
+        "ddc.RED_THREADS": source_constant("csrc_ddc/kdc_kernels.hpp", "RED_THREADS"),
+        "ddc.RED_WAVES": source_constant("csrc_ddc/kdc_kernels.hpp", "RED_WAVES"),
+        "ddc.RED_OUT": source_constant("csrc_ddc/kdc_kernels.hpp", "RED_OUT"),
+        "ddc.RED_CHUNK": source_constant("csrc_ddc/kdc_kernels.hpp", "RED_CHUNK"),
+        "demod.SPAN_FOUR": source_constant("csrc_demod/kdm_api.hip", "SPAN_FOUR"),
+        "demod.SPAN_TWO": source_constant("csrc_demod/kdm_api.hip", "SPAN_TWO"),
+        "demod.THREADS": source_constant("csrc_demod/kdm_kernels.hpp", "THREADS"),
+        "resamp.LDS_FOUR": source_constant("csrc_resamp/krs_kernels.hpp", "LDS_FOUR"),
+        "resamp.THREADS": source_constant("csrc_resamp/krs_kernels.hpp", "THREADS"),
+        "chan.LDS_TWO": source_constant("csrc_chan/kch_api.hip", "LDS_TWO"),
+        "chan.LDS_ONE": source_constant("csrc_chan/kch_api.hip", "LDS_ONE"),
+        "chan.WORK_VALUES": source_constant("csrc_chan/kch_api.hip", "WORK_VALUES"),
+        "chan.MAX_W": source_constant("csrc_chan/kch_api.hip", "MAX_W"),
+        "corr.THREADS": source_constant("csrc_corr/kcr_kernels.hpp", "THREADS"),
     }
 
 
@@ -65,6 +84,10 @@ EXPECTED_CONSTANTS = {
     "detect.STAGE_BYTES": 64 << 20, "mask.STAGE_BYTES": 64 << 20, "density.STAGE_BYTES": 64 << 20,
     "resamp.GRID_MAX": 1 << 20, "corr.WG_PER_CU": 16, "track.SCAN_THREADS": 1024, "track.THREADS": 256,
     "pulse.THREADS": 256, "pulse.PER": 8, "pulse.TILE": 2048,
+    "ddc.SPAN_SMALL": 7680, "ddc.SPAN_LARGE": 17408, "ddc.TILE_THREADS": 256, "ddc.RED_THREADS": 512, "ddc.RED_WAVES": 8,
+    "ddc.RED_OUT": 8, "ddc.RED_CHUNK": 8192, "demod.SPAN_FOUR": 9728, "demod.SPAN_TWO": 19968, "demod.THREADS": 256,
+    "resamp.LDS_FOUR": 40 * 1024, "resamp.THREADS": 256, "chan.LDS_TWO": 80 * 1024, "chan.LDS_ONE": 160 * 1024,
+    "chan.WORK_VALUES": 8192, "chan.MAX_W": 256, "corr.THREADS": 256,
 }
 
 
