@@ -193,7 +193,8 @@ int ksa_frames_c64(ksa_engine* e, const float* iq_host, int32_t nframes, int64_t
                    float* cur_db_host, float* hm_rows_host, int32_t commit);
 int ksa_frames_u8(ksa_engine* e, const uint8_t* iq_host, int32_t nframes, int64_t first_index, int64_t total_frames,
                   float* cur_db_host, float* hm_rows_host, int32_t commit);
-/* zeroSpanPlay (K:547-564 feeding K:469-484): accumulate an already computed linear spectrum. */
+/* zeroSpanPlay (K:547-564 feeding K:469-484): accumulate an already computed linear spectrum.  A magnitude below the
+ * smallest normal float32 (1.18e-38, under -380 dB) reads as zero: -inf dB. */
 int ksa_frame_spectrum(ksa_engine* e, const float* mag_host /* [fft_size], fftshifted */);
 /* Partial block of the last ksa_frames_dev(commit=0): float[4][N] = {max, cur-or--inf, -min, sum}
  * on the device -- all-reduce rows 0-2 with MAX (the minimum travels negated) and row 3 with SUM across
@@ -266,8 +267,9 @@ int ksa_scan_spectra_dev(ksa_engine* e, const void* iq_dev, int32_t fmt, int64_t
  * totalEntries).  own_db_dev = [npasses][step_hi-step_lo][N] dB spectra of its bands (own_band_major != 0:
  * [step_hi-step_lo][npasses][N], what one strided ksa_curscan_dev launch per band produces -- it lets a driver transform
  * the bands its neighbours wait for first and send them while the others are still being transformed); halo_db_dev =
- * [npasses][nhalo][N] spectra of the nhalo bands in front of step_lo that still cover owned elements (the overlap
- * K:645-650 averages: nhalo = ceil(N/hop) - 1 bands, 1 at the usual hop of N/2), received from the left neighbour.
+ * [nhalo][npasses][N] (band major, whatever own_band_major says) spectra of the nhalo bands in front of step_lo that
+ * still cover owned elements (the overlap K:645-650 averages: nhalo = ceil(N/hop) - 1 bands, 1 at the usual hop of
+ * N/2), received from the left neighbour.
  * Runs exactly the updates of K:643-668 on the owned elements only, and writes this engine's PARTIAL waterfall rows
  * (cell maxima over the owned elements, -inf where it owns none of a cell; K:696-697) for the batch's last
  * min(npasses,128) passes to rows_dev [rows][scan_hm_width] (engine scratch, see ksa_scan_rows_dev). */
@@ -305,9 +307,10 @@ int ksa_read_levels(ksa_engine* e, int32_t scan, int32_t mode, int32_t cells, fl
  * (0 cur, 1 max, 2 min, 3 avg; reduced to `cells` groups with `mode` as above) from its highest level down and
  * mark a cell unless an already marked one is closer than min_sep_cells (= pltHighsDelta4Marking * (x[-1]-x[0]) /
  * cell width, K:249-250, K:261-262), until `count` (<= 64) are marked (K:268-269).  As in the reference NaN sorts
- * above +inf and the lowest point is never visited (K:258).  Equal levels are taken higher index first; the reference's
- * order among equal levels is undefined (numpy's unstable argsort, K:251) and its spacing test runs on float64
- * frequencies, so tie order and a spacing of exactly min_sep_cells are parity-unpinned.
+ * above +inf and the lowest point is never visited (K:258).  Equal levels are taken higher index first, and +0.0 and -0.0
+ * are equal levels; the reference's order among equal levels is undefined (numpy's unstable argsort, K:251) and its
+ * spacing test runs on float64 frequencies, so tie order and a spacing of exactly min_sep_cells are parity-unpinned
+ * (INTEGRATION.md section 7).
  * idx_host / lvl_host: [count]; *found = cells marked. */
 int ksa_read_highs(ksa_engine* e, int32_t scan, int32_t mode, int32_t cells, int32_t curve, double min_sep_cells,
                    int32_t count, int32_t* idx_host, float* lvl_host, int32_t* found);

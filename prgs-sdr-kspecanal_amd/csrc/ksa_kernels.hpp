@@ -935,7 +935,7 @@ constexpr int HIGHS_MAX = 64;
 
 __device__ __forceinline__ unsigned order_bits(float v) {
   if (v != v) return 0xffffffffu;                       // NaN above everything
-  const unsigned u = __float_as_uint(v);
+  const unsigned u = v == 0.0f ? 0u : __float_as_uint(v);   // -0.0 and +0.0 are one level (equal in the reference's sort)
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);    // monotone map of the float order onto unsigned
 }
 

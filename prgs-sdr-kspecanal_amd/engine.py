@@ -549,6 +549,12 @@ class SpectrumEngine:
         out.update(fftHM=hm.astype(np.float64), hm_index=idx.value, passes=passes.value)
         return out
 
+    def scan_state_dev(self):
+        """Device views of the scan's persistent state (float32[4, totalEntries]: cur, max, min, avg) and of its ring."""
+        s, h = C.c_void_p(), C.c_void_p()
+        check(lib.ksa_scan_state_dev(self._h, C.byref(s), C.byref(h)))
+        return DevArray(s.value, (4, self.scan_total), self), DevArray(h.value, (HM_ROWS, self.scan_hm_width), self)
+
     def scan_reset(self):
         check(lib.ksa_scan_reset(self._h))
 
