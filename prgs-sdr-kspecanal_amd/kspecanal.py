@@ -63,7 +63,16 @@ dc|iq|dc+iq, zeroSpan only, not with `channels`, `correlate`, `pulses` or bUsePS
 corrector in front of everything else -- the sums of the first N blocks of the first batch (default all of it) are solved into a
 correction that every block of the run then gets before the engine (or `zoom`) sees it; with track every batch is corrected
 with the coefficients solved from the batch before it; handed off as d['iqfix'], a dict of per-solve arrays; default empty =
-off) and `iqfixSave` (an .npz of those arrays: batch, dc_i, dc_q, c, d, flags, count, sums, gain_db and phase_deg per solve).
+off) and `iqfixSave` (an .npz of those arrays: batch, dc_i, dc_q, c, d, flags, count, sums, gain_db and phase_deg per solve),
+`continuous` (true|false, zeroSpan only, not with bUsePSD true: the raw blocks of the run are read back to back -- no sample of
+the source is dropped between them (sources.ContiguousReader) -- and taken as ONE stream, and the stages that have a stream form
+run it with their state carried on the GPU from batch to batch: `zoom` and `channels` then capture exactly D x fullSize samples
+per frame, the mixer phase and the filter history run on, and channels keeps its start-up transient; `demod` and `audioRate`
+give seamless audio of ceil(frames x fullSize / audioDecim) samples (times L / M, rounded up) with no seam at a block edge;
+`pulses` and `correlate` find what straddles a block edge once, their records carry block -1 and positions counted from the
+run's first sample, and the hand-off flushes them, so that a pulse still on at the end is listed with its open-end flag; the
+engine takes every batch one frame per call, so that Fft.Avg is the per-frame recursion and nothing handed off depends on
+frameBatch; default false = every block is a capture of its own, the reference's model).
 The scan modes have keys of their own: `scanDetect` (T:G:THR[:mode=ca|go|so][:minWidth=W][:maxGap=K][:events=E][:edge=K][:dc=K],
 scan modes only: the CFAR detector of `detect` over every tuned band's dB row of every pass -- each band has its own gain and
 floor --, the band emissions mapped to the stitched range and the sightings that overlapping bands give of one emission joined
@@ -158,6 +167,7 @@ _KEYS = {
     "IQFIX": ("iqfix", str.lower), "IQFIXSAVE": ("iqfixSave", str),
     "SCANDETECT": ("scanDetect", str), "SCANDETECTSAVE": ("scanDetectSave", str),
     "SCANTRACK": ("scanTrack", str), "SCANTRACKSAVE": ("scanTrackSave", str),
+    "CONTINUOUS": ("continuous", _bool),
 }
 
 
@@ -177,7 +187,7 @@ def defaults():
         "detect": "", "detectSave": "", "demod": "", "demodSave": "", "channels": "", "channelsSave": "",
         "audioRate": "", "correlate": "", "correlateSave": "", "pulses": "", "pulsesSave": "",
         "track": "", "trackSave": "", "iqfix": "", "iqfixSave": "",
-        "scanDetect": "", "scanDetectSave": "", "scanTrack": "", "scanTrackSave": "",
+        "scanDetect": "", "scanDetectSave": "", "scanTrack": "", "scanTrackSave": "", "continuous": False,
     }
 
 
@@ -391,6 +401,16 @@ def _handle_mask(d):
     d["mask.spec"] = spec
 
 
+def _handle_continuous(d):
+    """continuous true|false (additive, zeroSpan only): the raw blocks of the run are one back-to-back stream and every stage
+    that has a stream form runs it.  It stands in front of the handlers whose specs it changes (zoom, channels, demod,
+    audioRate); false, the default, changes nothing."""
+    if not d["continuous"]:
+        return
+    if _gate(d, "continuous", "true", "the PSD diagnostic is per block"):
+        d["continuous"] = False
+
+
 ZOOM_RULE = ("zoom wants D[:offsetHz[:tapsPerPhase]] with an integer 1 <= D <= %d, a finite |offsetHz| <= samplingRate/2 and an "
              "integer 1 <= tapsPerPhase <= 16 with D x tapsPerPhase <= %d (defaults: offsetHz 0, tapsPerPhase 8); a batch of "
              "D x (fullSize - 1) + D x tapsPerPhase samples per frame must stay below 2^28 samples" % (MAX_DECIM, MAX_TAPS))
@@ -418,7 +438,8 @@ def _handle_zoom(d):
     if _gate(d, "zoom", text, "the PSD diagnostic sees the whole band"):
         return
     ntaps = decim * tpp
-    block_len = decim * (d["fullSize"] - 1) + ntaps
+    # continuous: the filter's history is carried from block to block, so a frame costs exactly decim x fullSize samples
+    block_len = decim * d["fullSize"] if d["continuous"] else decim * (d["fullSize"] - 1) + ntaps
     if d["frameBatch"] * block_len > MAX_IN:
         _refuse(d, "zoom", text, ZOOM_RULE)
     center, span = d["centerFreq"] + offset, d["samplingRate"] / decim
@@ -458,8 +479,11 @@ def _handle_channels(d):
         prg_quit(d, "ERROR:handle_args: channels [{}] and zoom [{}] exclude each other: either is the front end of the engine".format(
             text, d["zoom"]))
     decim, ntaps = nchan // over, nchan * tpb
-    first = -(-(ntaps - 1) // decim)
-    block_len = decim * (first + d["fullSize"] - 1) + 1
+    if d["continuous"]:                      # the stream form: no column is dropped, the start-up transient is part of the stream
+        first, block_len = 0, decim * d["fullSize"]
+    else:
+        first = -(-(ntaps - 1) // decim)
+        block_len = decim * (first + d["fullSize"] - 1) + 1
     if d["frameBatch"] * block_len > _chan.MAX_IN:
         _refuse(d, "channels", text, CHANNELS_RULE)
     offset = float(channel_freqs(nchan, d["samplingRate"])[pick])
@@ -705,14 +729,16 @@ def _handle_demod(d):
     ntaps = decim * tpp
     lead = 1 if mode == "fm" else 0
     front = d["zoom.spec"] if d["zoom.spec"] is not None else d["chan.spec"]       # channels stands in for zoom
-    if front is None or d["fullSize"] < ntaps + lead:
+    if front is None or (d["fullSize"] < ntaps + lead and not d["continuous"]):
         _refuse(d, "demod", text, DEMOD_RULE)
     exact = d["samplingRate"] / (front["decim"] * decim)
     rate = int(round(exact))
     if rate != exact:
         print("WARN:handle_args: demod [{}]: the audio rate [{}] is not an integer, the WAV file says [{}]".format(text, exact, rate))
+    # continuous: a call that takes the stream from N0 to N1 samples yields ceil(N1 / D) - ceil(N0 / D); this is the most of a block
+    per_block = -(-d["fullSize"] // decim) if d["continuous"] else (d["fullSize"] - lead - ntaps) // decim + 1
     d["demod.spec"] = dict(mode=mode, decim=decim, taps_per_phase=tpp, ntaps=ntaps, deemph_us=deemph,
-                           out_per_block=(d["fullSize"] - lead - ntaps) // decim + 1, rate=rate)
+                           out_per_block=per_block, rate=rate)
 
 
 RESAMPLE_RULE = ("audioRate wants HZ[:tapsPerPhase] with a whole HZ >= 1 and an integer tapsPerPhase >= 1 (default 8); it needs demod, "
@@ -748,9 +774,12 @@ def _handle_resample(d):
         P = len(resample_taps(L, M, tpp)) // L
     except KsaError as e:
         prg_quit(d, "ERROR:handle_args: audioRate [{}]: {}: {}".format(text, e, RESAMPLE_RULE))
-    per_block = -(-dspec["out_per_block"] * L // M) - -(-(P - 1) * L // M)
-    if per_block < 1:
-        _refuse(d, "audioRate", text, RESAMPLE_RULE)
+    if d["continuous"]:                      # the most a block of the stream can yield; no output is dropped
+        per_block = -(-dspec["out_per_block"] * L // M)
+    else:
+        per_block = -(-dspec["out_per_block"] * L // M) - -(-(P - 1) * L // M)
+        if per_block < 1:
+            _refuse(d, "audioRate", text, RESAMPLE_RULE)
     d["resample.spec"] = dict(rate=int(hz), rate_in=dspec["rate"], L=L, M=M, taps_per_phase=tpp, phase_taps=P,
                               in_per_block=dspec["out_per_block"], out_per_block=per_block)
 
@@ -872,7 +901,7 @@ def _handle_scan_track(d):
 
 
 # in the order handle_args calls them: a handler reads the specs of the ones before it (channels zoom's, demod either's, ...)
-_HANDLERS = (_handle_pfb, _handle_density, _handle_mask, _handle_zoom, _handle_channels, _handle_detect, _handle_demod,
+_HANDLERS = (_handle_pfb, _handle_density, _handle_mask, _handle_continuous, _handle_zoom, _handle_channels, _handle_detect, _handle_demod,
              _handle_resample, _handle_correlate, _handle_pulses, _handle_track, _handle_iqfix, _handle_scan_detect,
              _handle_scan_track)
 
@@ -897,6 +926,9 @@ def print_info(d):
     elif d["pfbTaps"]:
         print("INFO: pfbTaps [{}]: fullSize[{}] = pfbTaps x fftSize, prototype sinc x window[{}]".format(
             d["pfbTaps"], d["fullSize"], d["window"]))
+    if d.get("continuous"):
+        print("INFO: continuous [True]: the raw blocks are taken as one back-to-back stream and the stages run their stream forms "
+              "(zoom, channels, demod, audioRate, correlate, pulses); the per-block counts below are the most a block can yield")
     if d.get("zoom.spec"):
         z = d["zoom.spec"]
         print("INFO: zoom [{}]: span [{}] Hz around [{}] Hz, bin width [{}] Hz, low-pass of [{}] taps, [{}] samples per frame".format(
@@ -909,8 +941,9 @@ def print_info(d):
     if d.get("demod.spec"):
         m = d["demod.spec"]
         print("INFO: demod [{}]: audio decimation [{}], low-pass of [{}] taps, de-emphasis [{}] us, [{}] samples per block at [{}] Hz; "
-              "each block is demodulated on its own and the blocks abut".format(
-                  m["mode"], m["decim"], m["ntaps"], m["deemph_us"], m["out_per_block"], m["rate"]))
+              "{}".format(m["mode"], m["decim"], m["ntaps"], m["deemph_us"], m["out_per_block"], m["rate"],
+                          "the blocks are demodulated as one stream" if d.get("continuous") else
+                          "each block is demodulated on its own and the blocks abut"))
     if d.get("resample.spec"):
         r = d["resample.spec"]
         print("INFO: audioRate [{}]: [{}] Hz -> [{}] Hz by L / M = [{}] / [{}], [{}] taps per phase, [{}] samples per block".format(
@@ -1375,7 +1408,8 @@ def zero_span(d):
         for key, cls in _STAGES:
             if specs.get(key) is not None:
                 stages.append(cls(d, specs[key], run))
-        if stages or batch > 1:                  # every stage runs the batch route: frameBatch 1 is a batch of one
+        # every stage runs the batch route: frameBatch 1 is a batch of one; so does continuous, whose reader lives there
+        if stages or batch > 1 or (fused and d.get("continuous")):
             _zero_span_batches(d, eng, run, stages)
         else:
             _zero_span_frames(d, eng, freqs)
@@ -1562,11 +1596,13 @@ class _DetectFeed:
 
 def _gather_events(feed, obj, got):
     """What _CorrFeed and _PulseFeed do after a batch of `got` blocks went to their object: the events that are new are kept
-    with `block` counted over the run, not over the batch; where the object's list is full there is nothing to fetch."""
+    with `block` counted over the run, not over the batch; where the object's list is full there is nothing to fetch.  The
+    records of the stream form (feed.stream) stay as they are: block -1, positions counted over the stream."""
     if feed.stored < obj.capacity:
         ev = obj.events()[0]                         # synchronises: the buffer is free for the next batch
         new = ev[feed.stored:]
-        new["block"] += feed.blocks_done
+        if not feed.stream:
+            new["block"] += feed.blocks_done
         feed.parts.append(new)
         feed.stored = len(ev)
     else:
@@ -1576,21 +1612,29 @@ def _gather_events(feed, obj, got):
 
 class _CorrFeed:
     """The correlate key's state over a run: the Correlator, whose block form runs over every batch's raw blocks in their
-    iqFormat, read from the page-locked batch buffer; block numbers are frame numbers of the run."""
+    iqFormat, read from the page-locked batch buffer; block numbers are frame numbers of the run.  Under continuous the stream
+    form runs over the batch as one piece of the stream (kcr_process_dev, kcr_flush at the hand-off): block is -1 and pos
+    counts from the run's first sample."""
 
     def __init__(self, d, spec, run):
-        self.spec, self.full, self.rate = spec, d["fullSize"], d["samplingRate"]
+        self.spec, self.full, self.rate, self.stream = spec, d["fullSize"], d["samplingRate"], bool(d.get("continuous"))
         self.corr = Correlator(spec["templates"], threshold=spec["threshold"], guard=spec["guard"], capacity=spec["capacity"],
                                max_in=run.batch * self.full, fmt=run.fmt, device=d["device"])
         self.blocks_done, self.stored, self.parts = 0, 0, []
 
     def feed_raw(self, blocks, got):
         """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
-        self.corr.blocks_dev(blocks, got, self.full)
+        if self.stream:                              # the first `got` rows of the batch buffer are contiguous
+            self.corr.process_dev(blocks, got * self.full)
+        else:
+            self.corr.blocks_dev(blocks, got, self.full)
         _gather_events(self, self.corr, got)
 
     def handoff(self, d):
-        """The hand-off arrays, the INFO line, correlateSave."""
+        """The hand-off arrays, the INFO line, correlateSave.  The stream form first decides the lags still pending."""
+        if self.stream:
+            self.corr.flush()
+            _gather_events(self, self.corr, 0)
         _, total = self.corr.events()
         ev = np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=_corr.EVENT_DTYPE)
         d["corrEvents"], d["corrTotal"] = ev, total
@@ -1604,7 +1648,8 @@ class _CorrFeed:
             with open(d["correlateSave"], "wb") as f:
                 np.savez(f, events=ev, events_total=np.int64(total), toa=toa, templates=s["templates"],
                          threshold=np.float32(s["threshold"]), guard=np.int32(s["guard"]), capacity=np.int32(s["capacity"]),
-                         sampling_rate=np.float64(self.rate), block_len=np.int64(self.full))
+                         sampling_rate=np.float64(self.rate), block_len=np.int64(self.full),
+                         **({"continuous": np.bool_(True)} if self.stream else {}))   # toa: -1, stream position, seconds in
 
     def close(self):
         self.corr.close()
@@ -1613,10 +1658,13 @@ class _CorrFeed:
 class _PulseFeed:
     """The pulses key's state over a run: the PulseDetector, whose block form runs over every batch's raw blocks in their
     iqFormat, read from the page-locked batch buffer; block numbers are frame numbers of the run.  With rel: the levels are set
-    from the median envelope of the run's first block before any block is searched."""
+    from the median envelope of the run's first block before any block is searched.  Under continuous the stream form runs over
+    the batch as one piece of the stream (kpl_process_dev, kpl_flush at the hand-off): a pulse across a block edge is one
+    record, block is -1 and start counts from the run's first sample; rel: still measures the first block with the block form,
+    which does not touch the stream's state."""
 
     def __init__(self, d, spec, run):
-        self.spec, self.full, self.rate = spec, d["fullSize"], d["samplingRate"]
+        self.spec, self.full, self.rate, self.stream = spec, d["fullSize"], d["samplingRate"], bool(d.get("continuous"))
         on, off = (1.0, 1.0) if spec["rel"] else (_pulse.db_to_power(spec["on_db"]), _pulse.db_to_power(spec["off_db"]))
         self.det = PulseDetector(W=spec["W"], on_power=on, off_power=off, min_len=spec["min_len"], capacity=spec["capacity"],
                                  max_in=run.batch * self.full, fmt=run.fmt, device=d["device"])
@@ -1640,11 +1688,17 @@ class _PulseFeed:
         """blocks: the batch buffer, whose first `got` rows are the run's next blocks."""
         if self.spec["rel"] and self.floor is None:
             self._set_relative_levels(blocks)
-        self.det.blocks_dev(blocks, got, self.full)
+        if self.stream:                              # the first `got` rows of the batch buffer are contiguous
+            self.det.process_dev(blocks, got * self.full)
+        else:
+            self.det.blocks_dev(blocks, got, self.full)
         _gather_events(self, self.det, got)
 
     def handoff(self, d):
-        """The hand-off arrays, the INFO line, pulsesSave."""
+        """The hand-off arrays, the INFO line, pulsesSave.  The stream form first closes the pulse still open at the end."""
+        if self.stream:
+            self.det.flush()
+            _gather_events(self, self.det, 0)
         _, total, active = self.det.events()
         ev = np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=_pulse.EVENT_DTYPE)
         d["pulseEvents"], d["pulseTotal"], d["pulseActive"] = ev, total, active
@@ -1658,7 +1712,8 @@ class _PulseFeed:
                          on_db=np.float64(s["on_db"]), off_db=np.float64(s["off_db"]), W=np.int32(s["W"]),
                          min_len=np.int32(s["min_len"]), capacity=np.int32(s["capacity"]), thr_on=np.int64(thr_on),
                          thr_off=np.int64(thr_off), sampling_rate=np.float64(self.rate), block_len=np.int64(self.full),
-                         **_pulse.describe(ev, s["W"], self.rate, self.full))
+                         **({"continuous": np.bool_(True)} if self.stream else {}),
+                         **_pulse.describe(ev, s["W"], self.rate, 0 if self.stream else self.full))
 
     def close(self):
         self.det.close()
@@ -1724,10 +1779,12 @@ class _IqFeed:
 
 class _DemodFeed:
     """The demod key's state over a run: the Demodulator behind the down-converter, fed every batch's zoomed blocks in device
-    memory; each block is demodulated on its own and the blocks abut in the audio."""
+    memory; each block is demodulated on its own and the blocks abut in the audio.  Under continuous the blocks are one stream:
+    detector, filter history and the resampler's position are carried on the device from batch to batch."""
 
     def __init__(self, d, spec, run):
         self.spec, self.full, batch = spec, d["fullSize"], run.batch
+        self.stream = bool(d.get("continuous"))
         fs = d["samplingRate"] / run.front["decim"]
         taps = demod_taps(spec["decim"], spec["taps_per_phase"], deemph_us=spec["deemph_us"],
                           sampling_rate=fs if spec["deemph_us"] is not None else None, dc_block=spec["mode"] == "am")
@@ -1737,14 +1794,27 @@ class _DemodFeed:
         self.dem = Demodulator(spec["mode"], spec["decim"], taps, out_fmt="s16" if self.rspec is None else "f32",
                                pcm_scale=DEMOD_PCM_SCALE, max_in=batch * self.full, device=d["device"])
         if self.rspec is not None:                   # audioRate: float32 audio goes on to the resampler, which makes the int16
-            r = self.rspec
+            r = self.rspec                           # continuous: in_per_block is the most of a block, one more for the call's rounding
             self.res = Resampler(r["L"], r["M"], resample_taps(r["L"], r["M"], r["taps_per_phase"]), type="f32", out_fmt="s16",
-                                 pcm_scale=DEMOD_PCM_SCALE, max_in=batch * r["in_per_block"], device=d["device"])
+                                 pcm_scale=DEMOD_PCM_SCALE, max_in=batch * r["in_per_block"] + self.stream, device=d["device"])
         self.parts = []
+
+    def _feed_stream(self, iq_dev, got):
+        """The batch as the next got x fullSize samples of one stream (kdm_process_dev, then krs_process_dev): a call yields
+        ceil(N1 / D) - ceil(N0 / D) values, and the audio of the batches joins with no gap and no repeat."""
+        m = self.dem.process_dev(iq_dev, got * self.full)
+        if self.res is None:
+            self.parts.append(self.dem.read_out(m))
+            return
+        j = self.res.process_dev(self.dem._out, m)         # both on the NULL stream: the demodulator's values come first
+        self.parts.append(self.res.read_out(j))
 
     def feed(self, iq_dev, got, stride=None):
         """iq_dev: [got][fullSize] complex64 in device memory, the down-converter's own buffer (or, with a stride in values,
         one channel of every block of the channelizer's)."""
+        if self.stream:
+            assert stride is None                        # both front ends leave a continuous run's frames back to back
+            return self._feed_stream(iq_dev, got)
         m = self.dem.blocks_dev(iq_dev, got, self.full, block_stride=stride)
         if self.res is None:
             self.parts.append(self.dem.read_out(got * m))
@@ -1756,8 +1826,9 @@ class _DemodFeed:
         """The hand-off array, the INFO line, demodSave."""
         pcm = np.concatenate(self.parts) if self.parts else np.zeros(0, dtype=np.int16)
         d["demodAudio"], d["demodRate"] = pcm, self.rate
-        print("INFO:zero_span: demod [{}]: [{}] samples at [{}] Hz, [{}] per block, peak [{}]".format(
-            self.spec["mode"], len(pcm), self.rate, self.per_block, int(np.abs(pcm.astype(np.int32)).max()) if len(pcm) else 0))
+        print("INFO:zero_span: demod [{}]: [{}] samples at [{}] Hz, {}, peak [{}]".format(
+            self.spec["mode"], len(pcm), self.rate, "continuous" if self.stream else "[{}] per block".format(self.per_block),
+            int(np.abs(pcm.astype(np.int32)).max()) if len(pcm) else 0))
         if d["demodSave"]:
             write_wav(d["demodSave"], pcm, self.rate)
 
@@ -1769,17 +1840,22 @@ class _DemodFeed:
 
 class _ZoomFeed:
     """The zoom key's state over a run: the DownConverter in front of the engine, fed every batch's raw blocks -- or, behind
-    iqfix, the corrector's complex64 ones; its [got][fullSize] complex64 outputs go on from its own buffer."""
+    iqfix, the corrector's complex64 ones; its [got][fullSize] complex64 outputs go on from its own buffer.  Under continuous the
+    batch is the next got x block_len samples of one stream (kdc_process_dev): mixer phase and filter history carry on."""
 
     def __init__(self, d, spec, run):
-        self.block_len = spec["block_len"]
+        self.block_len, self.full, self.stream = spec["block_len"], d["fullSize"], bool(d.get("continuous"))
         fmt = FMT_C64 if d.get("iqfix.spec") is not None else run.fmt
         self.ddc = DownConverter(fmt, spec["decim"], ddc_lowpass(spec["decim"], spec["taps_per_phase"]), freq=spec["offset"],
                                  sampling_rate=d["samplingRate"], max_in=run.batch * self.block_len, device=d["device"])
 
     def front(self, src, got):
         """(address, no stride) of [got][fullSize] complex64; src is the batch buffer or the corrector's address."""
-        self.ddc.blocks_dev(src, got, self.block_len)
+        if self.stream:                              # block_len = decim x fullSize: every block yields exactly fullSize values
+            n = self.ddc.process_dev(src, got * self.block_len)
+            assert n == got * self.full, (n, got, self.full)
+        else:
+            self.ddc.blocks_dev(src, got, self.block_len)
         return self.ddc.out_ptr, None
 
     def handoff(self, d):
@@ -1791,16 +1867,24 @@ class _ZoomFeed:
 
 class _ChanFeed:
     """The channels key's state over a run: the Channelizer in front of the engine, fed every batch's raw blocks; the picked
-    channel of every block goes on as a strided view of its buffer, and every channel's power is summed over the run."""
+    channel of every block goes on as a strided view of its buffer, and every channel's power is summed over the run.  Under
+    continuous the batch is the next got x block_len samples of one stream (kch_process_dev): the picked channel is one row of
+    the bank's buffer, got x fullSize columns back to back."""
 
     def __init__(self, d, spec, run):
-        self.spec, self.full = spec, d["fullSize"]
+        self.spec, self.full, self.stream = spec, d["fullSize"], bool(d.get("continuous"))
         self.bank = Channelizer(run.fmt, spec["nchan"], spec["oversample"], chan_prototype(spec["nchan"], spec["taps_per_branch"]),
                                 max_in=run.batch * spec["block_len"], device=d["device"])
         self.power, self.values = np.zeros(spec["nchan"], dtype=np.float64), 0
 
     def front(self, blocks, got):
         """(address, stride in values) of the picked channel of every block: [got][M][fullSize] complex64 in the bank's buffer."""
+        if self.stream:
+            cols = self.bank.process_dev(blocks, got * self.spec["block_len"])
+            assert cols == got * self.full, (cols, got, self.full)
+            self.power += self.bank.channel_power(0, cols)
+            self.values += cols
+            return self.bank.out_ptr + 8 * self.spec["pick"] * self.bank.layout()[1], None
         cols = self.bank.blocks_dev(blocks, got, self.spec["block_len"])
         assert cols == self.full
         self.power += self.bank.channel_power(0, cols)
@@ -1853,6 +1937,21 @@ def _zero_span_frames(d, eng, freqs):
         _handoff(d, eng, freqs)                  # xRes-sized curves + markers + the new waterfall row (row f2)
 
 
+def _frames_one_by_one(eng, src, got, full_size, db):
+    """A continuous run's batch into the engine one frame per call.  The engine folds the average of a call in closed form
+    (ksa.h at ksa_frames_dev), whose float32 rounding depends on the frames per call; the reference's recursion (a + x) / 2 per
+    frame, which is what frameBatch 1 computes, does not.  A continuous run promises that nothing it hands off depends on how
+    it was cut into batches, so its Fft.Avg is the recursion's at every frameBatch; Cur, Max, Min and the waterfall are the same
+    either way.  src: a device address of [got][full_size] complex64 with db = the batch's [got][fftSize] row buffer or None --
+    or the page-locked batch itself (full_size None) with db = whether rows are wanted; the dB rows are returned, or None."""
+    if full_size is not None:
+        for i in range(got):
+            eng.frames_dev(src + 8 * i * full_size, FMT_C64, 1, cur_db=None if db is None else db[i:i + 1])
+        return db
+    out = [eng.frames(src[i:i + 1], cur_db=True)[0] if db else eng.frames(src[i:i + 1]) for i in range(got)]
+    return np.concatenate(out) if db else None
+
+
 def _zero_span_batches(d, eng, run, stages):
     """The batch route: up to run.batch blocks are read into ONE page-locked buffer and go through the engine and the stages in
     one pass; flags, the progress line and the plot refresh come once per batch.  prgLoopCnt still counts frames, and a source
@@ -1865,7 +1964,10 @@ def _zero_span_batches(d, eng, run, stages):
       int16 blocks are read by the kernels from the page-locked buffer), and returns the batch's dB rows if a row stage is on;
     - the demodulator (feed: demod, audioRate) reads the front end's blocks and keeps the batch's int16 audio on the host;
     - the row stages (feed_rows: density, mask, detect) read the dB rows; counts and events stay on the GPU until the hand-off;
-    - the raw stages (feed_raw: correlate, pulses) read the page-locked batch and keep the new events, block counted over the run."""
+    - the raw stages (feed_raw: correlate, pulses) read the page-locked batch and keep the new events, block counted over the run.
+    Under continuous the order is the same; the blocks come from one sources.ContiguousReader, which wastes no sample between
+    them, every stage that has a stream form takes the batch as the next piece of one stream (what it hands on has the same
+    shape), and the engine takes the batch one frame per call (_frames_one_by_one), so that Fft.Avg does not depend on frameBatch."""
     fix = next((s for s in stages if hasattr(s, "feed_raw") and hasattr(s, "out_ptr")), None)
     front = next((s for s in stages if hasattr(s, "front")), None)
     audio = next((s for s in stages if hasattr(s, "feed")), None)
@@ -1876,6 +1978,8 @@ def _zero_span_batches(d, eng, run, stages):
     stage = _engine.PinnedBuffer((run.batch, per * full), dtype)
     blocks = stage.array
     read_blocks = getattr(d["sdr"], "read_blocks", None)
+    if d.get("continuous"):                      # back to back: block i is samples [i, i + 1) x block_len after the settle read
+        read_blocks = sources.ContiguousReader(d["sdr"]).read_blocks
     try:
         done, prev = 0, time.time()
         while done < d["prgLoopCnt"]:
@@ -1904,10 +2008,15 @@ def _zero_span_batches(d, eng, run, stages):
                 if src is not blocks:                                        # [got][fullSize] complex64 in device memory
                     if rows:
                         db = eng._pinned_out("db", (got, d["fftSize"]))
-                    eng.frames_dev(src, FMT_C64, got, cur_db=db, frame_stride=stride)
+                    if d.get("continuous"):                                  # frame by frame, see _frames_one_by_one
+                        _frames_one_by_one(eng, src, got, d["fullSize"], db)
+                    else:
+                        eng.frames_dev(src, FMT_C64, got, cur_db=db, frame_stride=stride)
                     eng.synchronize()
                     if audio is not None:
                         audio.feed(src, got, stride)
+                elif d.get("continuous"):
+                    db = _frames_one_by_one(eng, blocks, got, None, bool(rows))
                 elif rows:
                     db = eng.frames(blocks[:got], cur_db=True)[0]
                 else:

@@ -163,3 +163,62 @@ class FileSdr(_SdrBase):
             except EOFError:
                 return i
         return k
+
+
+class ContiguousReader:
+    """read_blocks over any source with nothing thrown away: consecutive blocks are consecutive samples of the source, whatever
+    the block length.  The source is still asked only for reads the dongle allows (2^18 samples, or a power of two below that,
+    K:343); what such a read delivers beyond the end of a block is kept as the start of the next one.  At the end of a capture
+    the reads shrink through the allowed sizes, so that the padding of a read never costs samples the capture still holds.  One
+    reader serves one run: `raw` and the buffer's dtype do not change between calls."""
+
+    def __init__(self, sdr):
+        self.sdr = sdr
+        self._kept = None                                  # values read from the source and not yet handed out
+        self._cap = 2 ** 18                                # kspecanal.SDR_READ_UNIT, K:311; halved when the source refuses a read
+        self._exact = False                                # the source ran out once: reads are no longer rounded up
+        self._done = False
+
+    def _read(self, want, raw):
+        """`want` samples as sdr_read delivers them, flat: uint8 / int8 / int16 I,Q values or complex64."""
+        if raw in ("s8", "s16") and hasattr(self.sdr, "read_iq"):
+            return np.asarray(self.sdr.read_iq(want, raw), dtype=IQ_FORMATS[raw][0]).reshape(-1)
+        if raw is True and hasattr(self.sdr, "read_bytes"):
+            return np.asarray(self.sdr.read_bytes(2 * want), dtype=np.uint8).reshape(-1)
+        return np.asarray(self.sdr.read_samples(want)).astype(np.complex64).reshape(-1)
+
+    def _fill(self, row, per, raw):
+        """Fill `row` (whole samples of `per` values) from what was kept, then from the source; False when the source ran out."""
+        col = 0
+        if self._kept is not None:
+            col = min(len(self._kept), len(row))
+            row[:col] = self._kept[:col]
+            self._kept = self._kept[col:] if col < len(self._kept) else None
+        while col < len(row):
+            n = min((len(row) - col) // per, self._cap)
+            want = 1 << (n.bit_length() - 1) if self._exact else 1 << (n - 1).bit_length()
+            try:
+                part = self._read(want, raw)
+            except EOFError:
+                if want <= n:                              # fewer than `want` samples are left
+                    self._cap = want // 2
+                self._exact = True
+                if self._cap == 0:                         # not one: what this block got stays unused
+                    self._kept, self._done = np.array(row[:col]), True
+                    return False
+                continue
+            use = min(want, n) * per
+            row[col:col + use] = part[:use]
+            if use < len(part):
+                self._kept = np.array(part[use:])
+            col += use
+        return True
+
+    def read_blocks(self, k, length, raw, out):
+        """Fill out[:k] with the source's next k * length samples, in the values and dtype of kspecanal.sdr_read(sdr, length, raw).
+        Returns the number of whole blocks read before the end of the source; after that every call returns 0."""
+        per = 1 if out.dtype.kind == "c" else 2
+        for i in range(int(k)):
+            if self._done or not self._fill(out[i, :int(length) * per], per, raw):
+                return i
+        return int(k)
