@@ -15,7 +15,9 @@ samples: when something was on the air, in libksa_pulse.so; EmissionTracker (tra
 detector: its per-row emissions joined into time-frequency tracks, a signal list, in libksa_track.so; IqCorrector (iqfix.py)
 is the blind DC-offset and IQ-imbalance corrector in front of all of them: raw samples in, corrected complex64 out, and the
 integer sums the correction is solved from, in libksa_iqfix.so; ScanSurvey (survey.py) is the detector and the linker under a
-scan: the emissions of every tuned band joined over the stitched range, one list per pass, over those same libraries.
+scan: the emissions of every tuned band joined over the stitched range, one list per pass, over those same libraries;
+SpectrumMeter (measure.py) is the band meter beside the signal detector: channel power, occupied bandwidth, x-dB width, peak
+and power centroid of every emission or of fixed channels, in libksa_measure.so.
 """
 from ._lib import KsaError, lib, LIB_PATH, FMT_C64, FMT_U8, FMT_S8, FMT_S16, OUT_LINEAR, OUT_DB, OUT_DB_CLIP, HM_ROWS, CUMU_PFB, CUMU_PFB_PSD
 from .engine import (SpectrumEngine, PinnedBuffer, allreduce_state, scan_allstitch, scan_gather_state, full_size_for,
@@ -33,6 +35,7 @@ from .pulse import PulseDetector, PULSE_DTYPE, FLAG_OPEN_END, POWER_UNIT
 from .track import EmissionTracker, TRACK_DTYPE, SPAN_DTYPE, track_times_freqs      # track.FLAG_OPEN_END is the same bit 0
 from .iqfix import IqCorrector, imbalance_of
 from .survey import ScanSurvey, stitch_emissions
+from .measure import SpectrumMeter, RESULT_DTYPE, result_freqs, acpr
 
 __all__ = ["KsaError", "SpectrumEngine", "lib", "LIB_PATH", "FMT_C64", "FMT_U8", "FMT_S8", "FMT_S16", "OUT_LINEAR", "OUT_DB",
            "OUT_DB_CLIP", "HM_ROWS", "PinnedBuffer", "allreduce_state", "scan_allstitch", "scan_gather_state", "full_size_for", "window_starts", "window_table", "heatmap_width",
@@ -42,4 +45,4 @@ __all__ = ["KsaError", "SpectrumEngine", "lib", "LIB_PATH", "FMT_C64", "FMT_U8",
            "Channelizer", "chan_prototype", "channel_freqs", "Resampler", "resample_taps", "rate_ratio",
            "Correlator", "frequency_bank", "refine", "PulseDetector", "PULSE_DTYPE", "FLAG_OPEN_END", "POWER_UNIT",
            "EmissionTracker", "TRACK_DTYPE", "SPAN_DTYPE", "track_times_freqs", "IqCorrector", "imbalance_of",
-           "ScanSurvey", "stitch_emissions"]
+           "ScanSurvey", "stitch_emissions", "SpectrumMeter", "RESULT_DTYPE", "result_freqs", "acpr"]

@@ -72,7 +72,13 @@ give seamless audio of ceil(frames x fullSize / audioDecim) samples (times L / M
 `pulses` and `correlate` find what straddles a block edge once, their records carry block -1 and positions counted from the
 run's first sample, and the hand-off flushes them, so that a pulse still on at the end is listed with its open-end flag; the
 engine takes every batch one frame per call, so that Fft.Avg is the per-frame recursion and nothing handed off depends on
-frameBatch; default false = every block is a capture of its own, the reference's model).
+frameBatch; default false = every block is a capture of its own, the reference's model), `measure` (B[:xdb=X][:margin=M] with the
+occupied percentage 50 <= B < 100, zeroSpan only, needs `detect`: a band meter beside the detector -- after every batch the new
+emissions are measured on the GPU in the rows they were found in, each over its span widened by M bins (default 0) on either
+side: integrated power, power centroid, peak, the occupied bandwidth that holds B % of the power and the width X dB (default 3)
+below the peak; result i belongs to emission i; handed off as d['measureResults']; default empty = off) and `measureSave` (an
+.npz of the records, the parameters, and per record center_hz -- the power centroid --, obw_hz, xdb_hz, power_net_db -- the power
+less the detector's floor over the window -- and snr_db, that net power over the floor's).
 The scan modes have keys of their own: `scanDetect` (T:G:THR[:mode=ca|go|so][:minWidth=W][:maxGap=K][:events=E][:edge=K][:dc=K],
 scan modes only: the CFAR detector of `detect` over every tuned band's dB row of every pass -- each band has its own gain and
 floor --, the band emissions mapped to the stitched range and the sightings that overlapping bands give of one emission joined
@@ -128,6 +134,8 @@ from .track import EmissionTracker, track_times_freqs
 from . import iqfix as _iqfix
 from .iqfix import IqCorrector
 from .survey import ScanSurvey
+from . import measure as _measure
+from .measure import SpectrumMeter, result_freqs
 
 IQFORMATS = ("c64", "u8", "s8", "s16")      # s8 / s16: interleaved signed int8 (b / 128) / little-endian int16 (b / 32768) I,Q
 PRGMODES = ("ZEROSPAN", "ZEROSPANSAVE", "ZEROSPANPLAY", "SCAN", "FMSCAN", "QUICKFULLSCAN")
@@ -169,6 +177,8 @@ _KEYS = {
     "SCANTRACK": ("scanTrack", str), "SCANTRACKSAVE": ("scanTrackSave", str),
     "CONTINUOUS": ("continuous", _bool),
 }
+# the keys of the band meter, beside _KEYS: same grammar, looked up after it
+_KEYS_MEASURE = {"MEASURE": ("measure", str), "MEASURESAVE": ("measureSave", str)}
 
 
 def defaults():
@@ -188,6 +198,7 @@ def defaults():
         "audioRate": "", "correlate": "", "correlateSave": "", "pulses": "", "pulsesSave": "",
         "track": "", "trackSave": "", "iqfix": "", "iqfixSave": "",
         "scanDetect": "", "scanDetectSave": "", "scanTrack": "", "scanTrackSave": "", "continuous": False,
+        "measure": "", "measureSave": "",
     }
 
 
@@ -222,10 +233,10 @@ def handle_args(d, argv=None):
         cur = argv[i].upper()
         if cur in PRGMODES:
             d["prgMode"] = cur
-        elif cur in _KEYS:
+        elif cur in _KEYS or cur in _KEYS_MEASURE:
             if i + 1 >= len(argv):
                 prg_quit(d, "ERROR:handle_args: Missing value for [{}]".format(cur))
-            name, parse = _KEYS[cur]
+            name, parse = _KEYS[cur] if cur in _KEYS else _KEYS_MEASURE[cur]
             i += 1
             d[name] = parse(argv[i])
         else:
@@ -554,6 +565,45 @@ def _handle_track(d):
     if d["detect.spec"] is None:
         prg_quit(d, "ERROR:handle_args: track [{}] links the emissions of detect: give [detect T:G:THR] as well".format(text))
     d["track.spec"] = spec
+
+
+MEASURE_RULE = ("measure wants B with the occupied percentage 50 <= B < 100, optionally followed by :xdb=X (finite, 0..100 dB below "
+                "the peak, default 3) and :margin=M (an integer 0..%d bins on either side of the span, default 0), each at most "
+                "once" % _measure.MAX_MARGIN)
+
+
+def _handle_measure(d):
+    """measure B[:xdb=X][:margin=M] (additive, zeroSpan only, needs detect): d['measure.plan'] = dict(percent, occupied, xdb,
+    margin); when the key is off there is no such entry."""
+    d.pop("measure.plan", None)
+    text = d["measure"] or None
+    if not text:
+        if d["measureSave"]:
+            print("WARN:handle_args: measureSave [{}] is ignored without measure".format(d["measureSave"]))
+        return
+    plan = dict(percent=0.0, occupied=0.0, xdb=3.0, margin=0)
+    try:
+        parts = text.split(":")
+        plan["percent"] = float(parts[0])
+        seen = set()
+        for part in parts[1:]:
+            name, eq, value = part.partition("=")
+            name = name.lower()
+            if not eq or name not in ("xdb", "margin") or name in seen:
+                raise ValueError(part)
+            seen.add(name)
+            plan[name] = float(value) if name == "xdb" else int(value)
+        plan["occupied"] = float(np.float32(plan["percent"] / 100))      # the float32 the meter gets
+        if not (50 <= plan["percent"] < 100 and 0.5 <= plan["occupied"] < 1 and np.isfinite(plan["xdb"])
+                and 0 <= plan["xdb"] <= 100 and 0 <= plan["margin"] <= _measure.MAX_MARGIN):
+            raise ValueError(text)
+    except ValueError:
+        _refuse(d, "measure", text, MEASURE_RULE)
+    if _gate(d, "measure", text, "it reads the engine's own dB rows"):
+        return
+    if d["detect.spec"] is None:
+        prg_quit(d, "ERROR:handle_args: measure [{}] measures the emissions of detect: give [detect T:G:THR] as well".format(text))
+    d["measure.plan"] = plan
 
 
 CORR_RULE = ("correlate wants FILE.npy[:threshold[:guard[:events=N]]] with a finite 0 < threshold <= 1 (default 0.5), an integer "
@@ -902,7 +952,7 @@ def _handle_scan_track(d):
 
 # in the order handle_args calls them: a handler reads the specs of the ones before it (channels zoom's, demod either's, ...)
 _HANDLERS = (_handle_pfb, _handle_density, _handle_mask, _handle_continuous, _handle_zoom, _handle_channels, _handle_detect, _handle_demod,
-             _handle_resample, _handle_correlate, _handle_pulses, _handle_track, _handle_iqfix, _handle_scan_detect,
+             _handle_resample, _handle_correlate, _handle_pulses, _handle_track, _handle_measure, _handle_iqfix, _handle_scan_detect,
              _handle_scan_track)
 
 
@@ -1541,11 +1591,28 @@ class _DetectFeed:
         self.det = SignalDetector(d["fftSize"], spec["train"], spec["guard"], spec["threshold"], mode=spec["mode"],
                                   min_width=spec["min_width"], max_gap=spec["max_gap"], capacity=spec["capacity"],
                                   device=d["device"])
+        # the measure key: a meter whose result i belongs to the detector's emission i
+        self.plan, self.meter, self.measured = d.get("measure.plan"), None, 0
+        if self.plan is not None:
+            try:
+                self.meter = SpectrumMeter(d["fftSize"], capacity=spec["capacity"], occupied=self.plan["occupied"],
+                                           xdb=self.plan["xdb"], margin=self.plan["margin"], device=d["device"])
+            except Exception:
+                self.det.close()
+                raise
 
     def feed_rows(self, db):
         """db: float32 [k][fftSize], the dB rows of the run's next k frames."""
-        if len(db):
+        if not len(db):
+            return
+        if self.meter is None:
             self.det.detect_rows(db)
+            return
+        base = self.det.rows_seen
+        self.det.detect_rows(db)
+        # the batch's rows against the detector's buffer where it lies, from the emissions stored before the batch
+        self.meter.measure_detector(self.det, np.asarray(db, dtype=np.float32), row_base=base, first=self.measured)
+        self.measured = SpectrumMeter.detector_list(self.det)[3]
 
     def handoff(self, d):
         """The hand-off arrays, the INFO line, detectSave; then, with the track key, the link over these emissions."""
@@ -1564,8 +1631,33 @@ class _DetectFeed:
                          train=np.int32(s["train"]), guard=np.int32(s["guard"]), threshold_db=np.float32(s["threshold"]),
                          mode=np.array(s["mode"]), min_width=np.int32(s["min_width"]), max_gap=np.int32(s["max_gap"]),
                          center_hz=center, width_hz=width)
+        if self.meter is not None:
+            self.measure_handoff(d, ev)
         if d.get("track.spec") is not None:
             self.link(d)
+
+    def measure_handoff(self, d, ev):
+        """The measure key: the results of the stored emissions `ev`, the INFO line, measureSave."""
+        res = self.meter.results(0, len(ev))
+        d["measureResults"] = res
+        done = (res["flags"] & _measure.FLAG_MEASURED) != 0
+        obw = (res["obw_hi"] - res["obw_lo"] + 1)[done & (res["nvalid"] > 0)]
+        print("INFO:zero_span: measure spans measured [{}] / emissions [{}], median OBW [{}] bins, strongest power [{:.2f}] dB".format(
+            int(done.sum()), len(ev), float(np.median(obw)) if len(obw) else 0.0,
+            float(res["power_db"][done].max()) if done.any() else float("-inf")))
+        if d["measureSave"]:
+            width = (res["bin_hi"] - res["bin_lo"] + 1).astype(np.float64)
+            noise = width * np.power(10.0, ev["floor_db"].astype(np.float64) / 10.0)      # the floor over the window summed
+            net = np.where(done, res["power"] - noise, np.nan)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                net_db = np.where(net > 0, 10.0 * np.log10(np.where(net > 0, net, 1.0)), np.nan)
+                snr_db = np.where((net > 0) & (noise > 0), 10.0 * np.log10(np.where(net > 0, net, 1.0) / np.where(noise > 0, noise, 1.0)),
+                                  np.nan)
+            p = self.plan
+            with open(d["measureSave"], "wb") as f:
+                np.savez(f, results=res, occupied_percent=np.float64(p["percent"]), occupied=np.float32(p["occupied"]),
+                         xdb=np.float32(p["xdb"]), margin=np.int32(p["margin"]), power_net_db=net_db, snr_db=snr_db,
+                         **result_freqs(res, self.freqs))
 
     def link(self, d):
         """The track key: one link over the detector's whole buffer where it lies; the hand-off arrays, the INFO line,
@@ -1591,6 +1683,8 @@ class _DetectFeed:
                          row_period_s=np.float64(row_period_s), **track_times_freqs(tr, freqs, row_period_s))
 
     def close(self):
+        if self.meter is not None:
+            self.meter.close()
         self.det.close()
 
 
